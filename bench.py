@@ -20,14 +20,23 @@ seeded synthetic road graph of SURVEY.md §8d):
   melb300k (configs[0]-[2] stand-in): 548 x 548 spec-style graph, seed 1,
     `mod 3`; query leg with the .diff stand-in as for synth1m.
 
-One JSON line on rank 0: value = rows/s over all ranks; roofline for the
-dominant build kernel from HIP events, query_roofline for the walk kernel;
+One JSON line on rank 0: value = rows/s over all ranks, ms_per_step = one
+timed step; roofline for the dominant build kernel from the timed steps' HIP
+events.  A plain run does only that: set up, warm up, time the steps, print.
+
+--full adds every other leg: the table-search queries (queries_per_s and
+query_roofline for the walk kernel), the cpd-search legs, the PMC traffic
+passes, the end-to-end worker build and server, the parity sample, and
 cpu_baseline = the C oracle (OpenMP, all host threads of this job) on a
 bounded sample of the same workload, plus the configs[0] partitioned run
 (300k stand-in, mod 3: three workers one after another with every thread,
-then at once with a third each), rank 0 at N = 1 only.
+then at once with a third each), rank 0 at N = 1 only.  The --no-* switches
+drop single legs of a --full run.
+
+--dump-outputs DIR writes what the last timed step built (see dump_outputs).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                  [--full] [--dump-outputs DIR]
   (N > 1 is launched by torch.distributed.run; RANK/LOCAL_RANK/WORLD_SIZE)
 """
 import argparse
@@ -67,6 +76,11 @@ def parse(argv=None):
     ap.add_argument("--partkey", type=int, default=0)
     ap.add_argument("--batch", type=int, default=0,
                     help="rows per step (multiple of 1024); 0 = what fits in HBM, <= 28672")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the timed build steps: queries, cpd-search, "
+                         "PMC passes, end-to-end worker build, parity sample, CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's rows as DIR/<name>.npy (float64)")
     ap.add_argument("--queries", type=int, default=0, help="0 = the workload's")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every host thread this job may use (OMP_NUM_THREADS or affinity)")
@@ -363,11 +377,16 @@ def assemble(args, world, graph_info, B, elapsed_max, q_totals, q_ms_max, nrows,
                 "traffic_unit": "bytes/launch (PMC: 2*FETCH_SIZE + WRITE_SIZE, KiB->B)",
                 "traffic_scope": ("rank 0's GPU, one step of its own targets (every rank "
                                   "builds the same batch shape)" if world > 1 else "this GPU")
-                if t else "not collected (--no-pmc, no rocprofv3, or a shared-GPU rehearsal)",
+                if t else "not collected (no --full, --no-pmc, no rocprofv3, or a shared-GPU "
+                          "rehearsal)",
                 "launches": k["launches"],
                 "avg_launch_us": round(k["ms"] * 1e3 / max(1, k["launches"]), 3),
                 "bytes_per_launch": round(k["bytes"] / max(1, k["launches"]), 1)}
-    qps = q_totals[0] / (q_ms_max / 1e3) if q_ms_max > 0 else 0.0
+    if q_totals is None:  # a plain run has no query leg (--full)
+        qps = qmoves = None
+    else:
+        qps = round(q_totals[0] / (q_ms_max / 1e3) if q_ms_max > 0 else 0.0, 1)
+        qmoves = round(q_totals[2] / max(1.0, q_totals[0]), 1)
     wl = WORKLOADS[getattr(args, "workload", "synth1m")]
     return {
         "metric": METRIC,
@@ -391,8 +410,8 @@ def assemble(args, world, graph_info, B, elapsed_max, q_totals, q_ms_max, nrows,
                    "partition": f"{args.partmethod} {args.partkey}",
                    "parallelism": f"target-partition x{world} (no collective)"},
         "gteps": round(value * m / 1e9, 3),
-        "queries_per_s": round(qps, 1),
-        "query_mean_moves": round(q_totals[2] / max(1.0, q_totals[0]), 1),
+        "queries_per_s": qps,
+        "query_mean_moves": qmoves,
         "mean_runs_per_row": round(nruns / max(1, nrows), 1),
         "roofline": roof,
         "cpu_baseline": cpu,
@@ -940,6 +959,45 @@ def full_build_only(args, world, rank, local):
                           "wall_s": round(time.time() - t0, 3), "full_build": fb}), flush=True)
 
 
+DUMP_ROWS = 8               # sampled rows at most
+DUMP_MOVES_BYTES = 16e6     # budget of the sampled rows' compact moves (as float64)
+DUMP_RUNS_BYTES = 40e6      # budget of the sampled rows' runs (as float64)
+
+
+def dump_outputs(path, rows, targets):
+    """--dump-outputs: what the last timed step's build_rows() returned, as
+    float64 .npy files in `path` (every value is an integer below 2^53, so
+    exact), under 64 MB in all:
+      targets.npy           the batch's targets (row i's target node)
+      offsets.npy           every row's run offset (rows + 1 values: all the
+                            batch's run counts)
+      sample_rows.npy       a fixed seeded sample of row indices, sorted
+      sample_moves.npy      those rows in the compact form (rows.export_moves)
+      sample_run_counts.npy their run counts
+      sample_runs.npy       their RLE runs (rows.export_range), one row after
+                            another, each cut at the same fixed per-row cap
+    The whole batch is ~70 GB of runs at 1M nodes, hence the sample; the
+    offsets cover every row."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    nrows = rows.count()[0]
+    words = rows.move_words()
+    k = int(max(1, min(DUMP_ROWS, nrows, DUMP_MOVES_BYTES // (8 * words))))
+    cap = int(DUMP_RUNS_BYTES // (8 * k))
+    pick = np.sort(np.random.default_rng(12345).choice(nrows, size=k, replace=False))
+    moves, runs, counts = [], [], []
+    for r in pick:
+        moves.append(rows.export_moves(int(r), 1)[0])
+        _, rr = rows.export_range(int(r), 1)
+        counts.append(len(rr))
+        runs.append(rr[:cap])
+    out = {"targets": np.asarray(targets), "offsets": rows.offsets(), "sample_rows": pick,
+           "sample_moves": np.stack(moves), "sample_run_counts": np.asarray(counts),
+           "sample_runs": np.concatenate(runs)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
 def main():
     args = parse()
     if args.cpu_worker:
@@ -978,7 +1036,7 @@ def main():
         log(f"building hierarchy for {g.n} nodes / {g.m} edges on GPU {local} ...")
         build_plan_child(args, ppath, local)
     fb_xy = None
-    if not args.no_full_build and args.sample is None and local == 0:
+    if args.full and not args.no_full_build and args.sample is None and local == 0:
         fb_xy = full_build_xy(args)
     # PMC passes: children, before this process initialises the GPU.  At N > 1
     # on rank 0 only, on its own GPU (device 0 = local rank 0's), while the
@@ -995,7 +1053,7 @@ def main():
     # (the library's default share per rank would overcommit it)
     wf = 0.6 / world if share else 0.0
     traffic = None
-    if rank == 0 and local == 0 and not args.no_pmc:
+    if args.full and rank == 0 and local == 0 and not args.no_pmc:
         traffic = pmc_traffic(args)
     # CPD_BENCH_PG=1: the process group (RCCL) even at one rank, so the N>1
     # collectives' code path runs on a 1-GPU box too
@@ -1059,6 +1117,20 @@ def main():
     dev.timing(False)
     nrows, nruns = rows.count()
     last_targets = batch_of(owned, B, args.warmup + args.steps - 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rows, last_targets)
+
+    if not args.full:  # a plain run ends here: the timed steps' figures alone
+        if rank == 0:
+            out = assemble(args, world, (g.n, g.m), B, elapsed_max, None, 0.0, nrows, nruns,
+                           kt, None, None, pinfo, None)
+            out["lib_src_sha"] = cpd.lib_src_sha()
+            out["tree_src_sha"] = cpd.src_sha(ROOT)
+            out["ranks"] = ranks
+            emit_line(json.dumps(out))
+        if use_pg:
+            dist.destroy_process_group()
+        return
 
     # ---- table-search ------------------------------------------------------
     rng = np.random.default_rng(100 + rank)
