@@ -68,6 +68,95 @@ def tie_graph():
     return cpd.RoadGraph(g.row_ptr, g.dst, (g.w % 3 + 1).astype(np.uint32), g.x, g.y)
 
 
+def _path_edges(n, rng, wmax):
+    """A bidirectional path 0-1-...-(n-1), weights 1..wmax, in node order."""
+    edges = []
+    for v in range(n):
+        if v > 0:
+            edges.append((v, v - 1, int(rng.integers(1, wmax + 1))))
+        if v + 1 < n:
+            edges.append((v, v + 1, int(rng.integers(1, wmax + 1))))
+    return edges
+
+
+def chain_graph(n, seed):
+    """A bidirectional path 0-1-...-(n-1), weights 1..3: every row has a
+    handful of runs, each spanning thousands of columns — far past the
+    chunked RLE count's 16-column look-back guess."""
+    return graph_from_edges(n, _path_edges(n, np.random.default_rng(seed), 3))
+
+
+# The graphs below leave the out-degree <= 4 path (8- and 16-bit first-move
+# sets, 4-bit moves) at sizes of several 2048-column tiles.  They are not in
+# GRAPHS: that would multiply the whole parametrised suite and the pure-Python
+# CPU checks.  Tests name them directly; test_oracle_cpu.py pins what the GPU
+# tests rely on (degree band, tile count, runs per row).
+
+def lattice_wide(w, h, dmax, seed):
+    """A 4-neighbour w x h lattice (strongly connected); about 30% of the
+    nodes get extra out-edges, up to out-degree dmax, to nodes within +-3
+    cells.  Weights 1..29: many runs per row (no long stretch shares a move)."""
+    rng = np.random.default_rng(seed)
+    edges = []
+    for y in range(h):
+        for x in range(w):
+            a = y * w + x
+            nb = [(x + dx, y + dy) for dx, dy in ((1, 0), (-1, 0), (0, 1), (0, -1))
+                  if 0 <= x + dx < w and 0 <= y + dy < h]
+            for bx, by in nb:
+                edges.append((a, by * w + bx, int(rng.integers(1, 30))))
+            if rng.random() < 0.3:
+                near = [(bx, by) for bx in range(max(0, x - 3), min(w, x + 4))
+                        for by in range(max(0, y - 3), min(h, y + 4)) if (bx, by) != (x, y)]
+                extra = int(rng.integers(1, dmax - len(nb) + 1))
+                for i in rng.choice(len(near), size=extra, replace=False):
+                    edges.append((a, near[i][1] * w + near[i][0], int(rng.integers(1, 30))))
+    return graph_from_edges(w * h, edges)
+
+
+def chain_hub(n, hub_deg, seed):
+    """chain_graph plus one node (n // 2) of out-degree hub_deg, its extra
+    edges to random far endpoints: the hub sets the whole graph's first-move
+    set width, the rows stay a handful of runs spanning thousands of columns."""
+    rng = np.random.default_rng(seed)
+    edges = _path_edges(n, rng, 3)
+    hub = n // 2
+    for b in rng.choice(n, size=hub_deg - 2, replace=False):
+        edges.append((hub, int(b), int(rng.integers(1, 4))))
+    return graph_from_edges(n, edges)
+
+
+def comb(n, every, dmax, reach, seed):
+    """chain_graph's path with every `every`-th node given 3..dmax-2 extra
+    out-edges within +-reach, weights 1..199: runs of a few to a few dozen
+    columns, stretches with and without breaks alternating inside one tile."""
+    rng = np.random.default_rng(seed)
+    edges = _path_edges(n, rng, 3)
+    for a in range(every // 2, n, every):
+        for _ in range(int(rng.integers(3, dmax - 1))):
+            b = a
+            while b == a:
+                b = int(rng.integers(max(0, a - reach), min(n, a + reach + 1)))
+            edges.append((a, b, int(rng.integers(1, 200))))
+    return graph_from_edges(n, edges)
+
+
+# name -> (graph, first-move set bits, 2048-column tiles, targets the GPU test builds)
+WIDE = {
+    "lattice8": (lambda: lattice_wide(80, 80, 8, seed=8), 8, 4, 2500),
+    "lattice15": (lambda: lattice_wide(80, 80, 15, seed=15), 16, 4, 2500),
+    "hub8": (lambda: chain_hub(34000, 8, seed=8), 8, 17, 300),
+    "hub12": (lambda: chain_hub(34000, 12, seed=12), 16, 17, 300),
+    "comb8": (lambda: comb(10000, 53, 8, 300, seed=8), 8, 5, 400),
+    "comb15": (lambda: comb(10000, 53, 15, 300, seed=15), 16, 5, 400),
+}
+
+
+def wide_targets(name, g):
+    """The shuffled targets the GPU tests build for WIDE[name]."""
+    return np.random.default_rng(1).permutation(g.n).astype(np.uint32)[:WIDE[name][3]]
+
+
 GRAPHS = {
     "synth": lambda: cpd.synth_road_graph(40, 30, seed=7),
     "ties": tie_graph,

@@ -12,7 +12,7 @@ import pytest
 
 import cpd
 import oracle
-from graphs import GRAPHS, graph_from_edges
+from graphs import GRAPHS, chain_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -308,20 +308,6 @@ def test_narrow_rows_switched_off_when_mostly_wide(scale, narrow_kept):
         np.testing.assert_array_equal(runs, ref_runs)
         if rep == 1:
             assert ("group_rows" in dev.timing_get()) == narrow_kept
-
-
-def chain_graph(n, seed):
-    """A bidirectional path 0-1-...-(n-1), weights 1..3: every row has a
-    handful of runs, each spanning thousands of columns — far past the
-    chunked RLE count's 16-column look-back guess."""
-    rng = np.random.default_rng(seed)
-    edges = []
-    for v in range(n):
-        if v > 0:
-            edges.append((v, v - 1, int(rng.integers(1, 4))))
-        if v + 1 < n:
-            edges.append((v, v + 1, int(rng.integers(1, 4))))
-    return graph_from_edges(n, edges)
 
 
 @pytest.mark.parametrize("n", [5000, 20000])

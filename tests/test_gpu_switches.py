@@ -18,6 +18,12 @@ oracle, walk queries over them dense and RLE.  What each reaches:
   CPD_OVERLAP=0   each batch's up-sweep on the main stream, after the previous
                   batch's first moves (no second up store in use)
   CPD_FM_ORDER=0  first_moves' segments in column order (not Hilbert order)
+Both graphs have one 2048-column tile and one 1024-target slab.  Past that:
+test_unfused_rle_past_one_tile (below) runs CPD_RLE_FUSED=0 over 3 and 17
+tiles; rle_scan<8|16>, rle_moves<8|16> (second 16-tile chunk included),
+first_moves<8|16,1,true|false> and first_moves<4,2,false> at a second slab
+are reached by tests/test_gpu_wide_degree.py, cpd_search<1|3|4,*> by
+tests/test_gpu_search_widths.py (<2,*>: tests/test_gpu_search.py).
 Round 6 removed the switches whose variants lost their A/Bs (VERDICT r05
 item 7): CPD_FM_N4, CPD_RLE_CH, CPD_MOVES_SWAR, CPD_TABLE_BITS, CPD_TS_SHARE,
 CPD_EMIT_DEFER, CPD_UP_HEAD, CPD_EMIT_WIDE, CPD_ROWS_NIBBLE (and the schedule
@@ -89,3 +95,55 @@ def test_switch_off_bit_exact(switch):
     assert p.returncode == 0, p.stderr[-2000:]
     res = json.loads(p.stdout.strip().splitlines()[-1])
     assert res == {"synth": True, "deg8": True}, (switch, res)
+
+
+# CPD_RLE_FUSED=0 past one tile.  The graphs above have one 2048-column tile
+# (synth: 2 count chunks), so the unfused 4-bit path's tile carries and its
+# second 16-tile chunk would go unrun now that the fused emit is the default:
+#   synth70  4900 nodes: 3 tiles, 6 chunks of rle_count_ch<32>, seams for rle_fix
+#   chain    34000 nodes: 17 tiles = 2 chunks of rle_moves4, 3 grid columns of
+#            rle_count_ch<32>; a handful of runs per row, far past rle_fix's rescan
+#            budget, so the gated rle_scan<4> re-counts the batch
+#   hub8     the same path with a degree-8 node: rle_scan<8> + rle_moves<8>
+#            (what the switch must leave alone)
+CHILD_UNFUSED = r"""
+import json, sys
+import numpy as np
+sys.path[:0] = [%r, %r, %r]
+import cpd, oracle
+from graphs import chain_graph, chain_hub
+out = {}
+for name, make, k in (("synth70", lambda: cpd.synth_road_graph(70, 70, seed=70), 1500),
+                      ("chain", lambda: chain_graph(34000, seed=34), 300),
+                      ("hub8", lambda: chain_hub(34000, 8, seed=8), 300)):
+    g = make()
+    plan = cpd.Plan(g)
+    dev = cpd.Graph(plan, batch=1024)
+    targets = np.random.default_rng(4).permutation(g.n).astype(np.uint32)[:k]
+    rows = dev.build_rows(targets)
+    off, runs = rows.export()
+    ref_off, ref_runs = oracle.build_rows(g.row_ptr, g.dst, g.w, plan.order(), targets)
+    mv = rows.export_moves()
+    ref_mv = oracle.moves_from_runs(ref_off, ref_runs, g.n, rows.move_bits())
+    out[name] = {"offsets": bool(np.array_equal(off, ref_off)),
+                 "runs": bool(np.array_equal(runs, ref_runs)),
+                 "moves": bool(np.array_equal(mv, ref_mv)),
+                 "tiles": (g.n + 2047) // 2048, "bits": rows.move_bits(),
+                 "runs_per_row": float(ref_off[-1]) / k}
+print(json.dumps(out))
+"""
+
+
+def test_unfused_rle_past_one_tile():
+    code = CHILD_UNFUSED % (HERE, os.path.join(ROOT, "distributed-oracle-search_amd"),
+                            os.path.join(ROOT, "oracle"))
+    env = dict(os.environ, CPD_RLE_FUSED="0")
+    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    res = json.loads(p.stdout.strip().splitlines()[-1])
+    shape = {k: (v["tiles"], v["bits"]) for k, v in res.items()}
+    assert shape == {"synth70": (3, 2), "chain": (17, 1), "hub8": (17, 4)}, shape
+    assert res["chain"]["runs_per_row"] < 8 and res["hub8"]["runs_per_row"] < 16
+    for name, v in res.items():
+        assert v["offsets"] and v["runs"] and v["moves"], (name, v)

@@ -255,3 +255,29 @@ def test_search_virtual_time_limit():
         c, _, _, st = oracle.cpd_search(g.row_ptr, g.dst, g.w, wc, order, T, off, runs, s, t, **kw)
         np.testing.assert_array_equal(c, c0)
         np.testing.assert_array_equal(st, st0)
+
+
+@pytest.mark.parametrize("name", ["lattice8", "lattice15", "hub8", "hub12", "comb8", "comb15"])
+def test_wide_degree_generators_keep_their_shape(name):
+    """What tests/test_gpu_wide_degree.py relies on, from the oracle alone: a
+    changed generator must not quietly take the GPU tests back to one tile,
+    to 4-bit sets, or to rows without long (or without many) runs."""
+    from graphs import WIDE, wide_targets
+    make, set_bits, tiles, _ = WIDE[name]
+    g = make()
+    deg = int(np.diff(g.row_ptr.astype(np.int64)).max())
+    assert (5 <= deg <= 8) if set_bits == 8 else (9 <= deg <= 15)
+    assert (g.n + 2047) // 2048 == tiles
+    order = oracle.dfs_preorder(g.row_ptr, g.dst)
+    targets = wide_targets(name, g)
+    off, runs = oracle.build_rows(g.row_ptr, g.dst, g.w, order, targets)
+    per_row = np.diff(off.astype(np.int64))
+    if name.startswith("hub"):
+        assert tiles > 16                      # a second 16-tile chunk of the move emit
+        assert per_row.max() < 16
+    elif name.startswith("comb"):
+        assert 16 < g.n / per_row.mean() < 2048  # past the 16-column look-back guess
+    else:
+        assert per_row.min() > 0.3 * g.n
+    for t in targets[:3]:  # strongly connected
+        assert oracle.reverse_dijkstra(g.row_ptr, g.dst, g.w, t).max() != oracle.INF
