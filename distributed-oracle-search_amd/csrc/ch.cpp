@@ -19,7 +19,6 @@
 // count: every adjacency list is kept sorted and merges are grouped by owner.
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <numeric>
@@ -29,6 +28,7 @@
 #endif
 
 #include "cpd_internal.hpp"
+#include "cpd_switches.hpp"
 
 namespace cpd {
 namespace {
@@ -163,17 +163,11 @@ struct Contractor {
         return count;
     }
 
-    // priority = a*edge difference + b*contracted neighbours + c*depth; depth
-    // bounds the sweep levels.  Round 3 (profiles/ch_prio_ab/): 8,2,12 —
-    // 166 + 159 levels, 5.20M arcs, 343k rows/s on the 1M bench graph —
-    // against round 2's 8,2,3 (189 + 194 levels, 5.09M arcs, 338k rows/s):
-    // fewer latency-bound narrow levels outweigh 2% more arcs (8,2,20 / 8,2,30:
-    // 343-345k / 345.6k, with the down-sweep's arcs and time growing).
-    int64_t prio_ed = 8, prio_del = 2, prio_depth = 12;
+    const ChPrio pw = ch_prio();  // the priority's weights (cpd_switches.hpp)
 
     int64_t priority_of(uint32_t v, int64_t sc) const {
         int64_t ed = sc - (int64_t)in[v].size() - (int64_t)out[v].size();
-        return prio_ed * ed + prio_del * (int64_t)deleted[v] + prio_depth * (int64_t)depth[v];
+        return pw.ed * ed + pw.deleted * (int64_t)deleted[v] + pw.depth * (int64_t)depth[v];
     }
     int64_t priority(uint32_t v, Witness& ws) const {
         return priority_of(v, shortcuts(v, nullptr, settle_sim, nullptr, ws));
@@ -229,14 +223,6 @@ Hierarchy build_hierarchy(uint32_t n, const uint32_t* row_ptr, const uint32_t* d
     C.depth.assign(n, 0);
     C.settle_contract = settle_limit ? settle_limit : 400;
     C.settle_sim = std::max<uint32_t>(50, C.settle_contract / 4);
-    if (const char* e = std::getenv("CPD_CH_PRIO")) {  // tuning knob: "ed,deleted,depth"
-        long a, b, c;
-        if (std::sscanf(e, "%ld,%ld,%ld", &a, &b, &c) == 3) {
-            C.prio_ed = a;
-            C.prio_del = b;
-            C.prio_depth = c;
-        }
-    }
 
     // Internal ids (see Contractor::orig): lab[node] = DFS preorder position.
     std::vector<uint32_t> lab(n);

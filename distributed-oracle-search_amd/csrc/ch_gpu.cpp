@@ -27,6 +27,7 @@
 
 #include "ch_kernels.hpp"
 #include "cpd_internal.hpp"
+#include "cpd_switches.hpp"
 
 namespace cpd {
 namespace {
@@ -100,15 +101,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
     const double t0 = now_seconds();
     const uint32_t settle_c = settle_limit ? settle_limit : 400;
     const uint32_t settle_s = std::max<uint32_t>(50, settle_c / 4);
-    int64_t pa = 8, pb = 2, pc = 12;  // ch.cpp Contractor::prio_* (CPD_CH_PRIO as there)
-    if (const char* e = std::getenv("CPD_CH_PRIO")) {
-        long a, b, c;
-        if (std::sscanf(e, "%ld,%ld,%ld", &a, &b, &c) == 3) {
-            pa = a;
-            pb = b;
-            pc = c;
-        }
-    }
+    const ChPrio pw = ch_prio();  // as ch.cpp's Contractor::prio_*
 
     // Initial overlay (ch.cpp: no self loops, parallel edges reduced to the
     // lightest, lists sorted by neighbour id): out-lists at [0, M), in-lists
@@ -245,8 +238,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
     const uint64_t lb1 = chk::witness_lane_bytes(caps1);
     // lanes: up to 262144 (4096 waves: 6.4 GB of workspaces), fewer for small
     // graphs (a round has at most ~4n searches)
-    uint64_t lane_max = 262144;  // CPD_CH_LANES (1M: 65536 / 131072 / 262144 lanes: 1.30 / 1.20 / 1.18 s)
-    if (const char* e = std::getenv("CPD_CH_LANES")) lane_max = std::max(256ul, std::strtoul(e, nullptr, 10));
+    constexpr uint64_t lane_max = 262144;  // 1M: 65536 / 131072 / 262144 lanes: 1.30 / 1.20 / 1.18 s
     const uint32_t lanes1 =
         (uint32_t)std::min<uint64_t>(lane_max, std::max<uint64_t>(256, (4ull * n + 255) / 256 * 256));
     DBuf<uint8_t> ws1, ws2;
@@ -271,9 +263,8 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
     const bool no_wave = std::getenv("CPD_CH_NOWAVE") != nullptr;
     if (no_wave) wave_max = 0;
     // pops + relaxations a lane search may take before a wave takes it over
-    // (A/B at 1M nodes: 512 -> 2.6 s, 2048 -> 2.4 s, none -> 2.1 s: default none)
-    uint32_t lane_cap = 0xFFFFFFFFu;
-    if (const char* e = std::getenv("CPD_CH_LANE_CAP")) lane_cap = (uint32_t)std::strtoul(e, nullptr, 10);
+    // (A/B at 1M nodes: 512 -> 2.6 s, 2048 -> 2.4 s, none -> 2.1 s: none kept)
+    constexpr uint32_t lane_cap = 0xFFFFFFFFu;
     uint64_t wave_searches = 0;
     double t_lane = 0, t_wave = 0, t_big = 0;  // witness kernel wall times (verbose)
     DBuf<uint32_t> ovf3;
@@ -291,7 +282,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
                 tag1 = 0;
             }
             chk::launch_witness(pairs.p, nullptr, np, overlay(), state.p, contract, settle, ws1.p,
-                                caps1, lanes1, tag1, no_wave ? 0xFFFFFFFFu : lane_cap, slots.p,
+                                caps1, lanes1, tag1, lane_cap, slots.p,
                                 sflag.p, sc.p, ovf.p, ctr.p, ctr.p + 1, st);
             tag1 += np + 1;
             read({ctr.p});
@@ -368,7 +359,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
         pairs.ensure(4ull * std::max(np, 1u));
         chk::launch_make_pairs(list, k, overlay(), s[0].p, nullptr, pairs.p, st);
         witness(np, false, settle_s);
-        chk::launch_prio(list, k, overlay(), sc.p, deleted.p, depth.p, pa, pb, pc, prio.p, aff.p,
+        chk::launch_prio(list, k, overlay(), sc.p, deleted.p, depth.p, pw.ed, pw.deleted, pw.depth, prio.p, aff.p,
                          cnt_o.p, cnt_i.p, cur_o.p, cur_i.p, st);
     };
 

@@ -1007,12 +1007,6 @@ void launch_witness_wave(const uint32_t* pairs, const uint32_t* plist, uint32_t 
                                    sflag, sc, ovf, ovf_n, err, s);
 }
 
-uint32_t witness_wave_lds_bytes(int size) {
-    return size == 0 ? (uint32_t)sizeof(WaveLds<512, 384, 32>)
-           : size == 1 ? (uint32_t)sizeof(WaveLds<1024, 768, 64>)
-                       : (uint32_t)sizeof(WaveLds<2048, 1792, 128>);
-}
-
 void launch_record(const uint32_t* S, uint32_t nS, uint32_t rank0, Overlay g, const uint32_t* upos,
                    const uint32_t* dpos, uint64_t ubase, uint64_t dbase, uint32_t* rank,
                    uint32_t* rec_v, uint64_t* rec_uo, uint32_t* rec_un, uint64_t* rec_do,

@@ -20,6 +20,7 @@
 
 #include "cpd_internal.hpp"
 #include "cpd_kernels.hpp"
+#include "cpd_switches.hpp"
 
 using namespace cpd;
 
@@ -154,31 +155,10 @@ struct Agg {
     double ms = 0.0, bytes = 0.0;
 };
 
-bool async_on();  // CPD_ASYNC (defined with the other switches)
 hipStream_t thread_stream(int device);
 
-// Largest auto batch (CPD_BATCH_MAX, a multiple of 1024 <= 32768; A/B knob).
-// 28672 since the rows are built at the packed width (8.0 MB per target at
-// 1M nodes; profiles/batch_ab/r05am: 387.3k against 380.8k rows/s at 24576).
-uint32_t batch_max() {
-    static const uint32_t v = [] {
-        const char* e = std::getenv("CPD_BATCH_MAX");
-        const unsigned long b = e && *e ? std::strtoul(e, nullptr, 10) : 28672ul;
-        return (uint32_t)std::max(1024ul, std::min(32768ul, b / 1024ul * 1024ul));
-    }();
-    return v;
-}
-
-// CPD_RLE_FUSED=0: the count / seam repair / emit passes instead of the
-// fused one-pass emit (4-bit sets; A/B, identical rows)
-bool rle_fused_on() {
-    static const bool on = [] {
-        const char* e = std::getenv("CPD_RLE_FUSED");
-        return !(e && *e == '0');
-    }();
-    return on;
-}
-bool rle_fused(uint32_t fmb) { return fmb == 4 && rle_fused_on(); }
+// the fused one-pass emit: 4-bit sets only (CPD_RLE_FUSED=0: never)
+bool rle_fused(uint32_t fmb) { return fmb == 4 && switches().rle_fused; }
 
 // Pool rows (1 KiB: one 256-target group row kept 32-bit) of a narrow batch
 // of B targets: an eighth of its group rows, and at least every group row of
@@ -206,9 +186,6 @@ double batch_bytes_per_row(uint32_t n, uint32_t n_up, uint32_t npad, uint32_t fm
     return fin + 8.0 * n_up + 3.0 * fmb / 8.0 * npad + rle + (leaf_fm ? 0.5 * n : 0.0) +
            2.0 * mbits / 8.0 * npad;
 }
-bool lane_key_on();
-bool seg_order_on();
-bool search_trace();
 std::vector<uint32_t> hilbert_keys(const int32_t* x, const int32_t* y, uint32_t n);
 
 }  // namespace
@@ -533,7 +510,7 @@ struct cpd_graph {
             CPD_REQUIRE(hbm_reserve == 0 || fit >= 1024.0, CPD_E_OOM,
                         "HBM reserve of " + std::to_string(hbm_reserve >> 20) + " MiB leaves " +
                             std::to_string((size_t)avail >> 20) + " MiB: too little for a 1024-row batch");
-            want = (uint32_t)std::min((double)batch_max(), std::max(1024.0, std::floor(fit / 1024) * 1024));
+            want = (uint32_t)std::min((double)switches().batch_max, std::max(1024.0, std::floor(fit / 1024) * 1024));
         }
         want = (want + 1023u) / 1024u * 1024u;
         if (want == B && upx[0].p) return;
@@ -557,7 +534,7 @@ struct cpd_graph {
             if (x >= 1) {
                 size_t free_b = 0, total_b = 0;
                 HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-                if (!(async_on() && set_bytes * 8 < (free_b > hbm_reserve ? free_b - hbm_reserve : 0))) {
+                if (!(switches().async && set_bytes * 8 < (free_b > hbm_reserve ? free_b - hbm_reserve : 0))) {
                     for (uint32_t y = x; y < kSets; ++y) {
                         fmx[y].release();
                         rle_stx[y].release();
@@ -801,14 +778,6 @@ namespace {
 constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kL1Bit = 0x40000000u;
 
-// Optimisation switches for A/B runs: CPD_<NAME>=0 turns one off (CPD_LIVE,
-// CPD_SORT, CPD_LEAFFM here, CPD_XCD in the launchers); results are identical
-// either way.
-bool env_on(const char* name) {
-    const char* e = std::getenv(name);
-    return !(e && *e == '0');
-}
-
 // One non-blocking stream per (host thread, device), kept for the thread's
 // lifetime: exports from several host threads never queue behind a build's
 // stream or each other.
@@ -853,7 +822,7 @@ std::vector<uint32_t> level_order(const cpd_plan& p, const std::vector<uint32_t>
 // leaf_edges (descending only): a leaf's list is its out-edges in file order
 // (self loops and parallel edges included) instead of its up-arcs — the same
 // minimum, and the list position is the move index for the leaf's first-move
-// set (the down-sweep computes leaf sets, cpd_kernels.hip sweep_down8c).
+// set (the down-sweep computes leaf sets, cpd_kernels.hip sweep_down8).
 // Nodes of up-level >= 2 own a row of the compact up store, u = ascending
 // slot - ubase: ascending arcs into them carry u; uidx (descending only)
 // gets each slot's u (~0 for the closed forms).
@@ -1032,10 +1001,6 @@ int cpd_batch_bytes(uint32_t n, uint32_t max_degree, uint32_t batch, uint64_t* b
     });
 }
 
-namespace {
-bool trace_on();
-}  // namespace
-
 int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
     return guarded([&] {
         CPD_REQUIRE(p && out, CPD_E_ARG, "graph: null argument");
@@ -1071,7 +1036,7 @@ int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
         for (hipEvent_t* e : {&g->ev_up, &g->ev_down, &g->ev_fm[0], &g->ev_fm[1]})
             HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         for (auto& e : g->ev_emit) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (trace_on()) std::fprintf(stderr, "[cpd] graph streams %.3f s\n", now_seconds() - tg0);
+        if (switches().trace) std::fprintf(stderr, "[cpd] graph streams %.3f s\n", now_seconds() - tg0);
         const uint32_t n = p->n, m = p->m;
         g->n = n;
         g->m = m;
@@ -1112,7 +1077,7 @@ int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
         std::vector<uint32_t> adj = g->packed_adjacency(g->w_free_col);
         g->adj.upload(adj.data(), adj.size(), s);
         HIP_CHECK(hipStreamSynchronize(s));
-        if (trace_on()) std::fprintf(stderr, "[cpd] graph csr+adjacency %.3f s\n", now_seconds() - tg0);
+        if (switches().trace) std::fprintf(stderr, "[cpd] graph csr+adjacency %.3f s\n", now_seconds() - tg0);
         g->has_ch = !p->ch.rank.empty();
         if (!g->has_ch) {  // query-only graph (fifo_auto)
             *out = g.release();
@@ -1131,7 +1096,7 @@ int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
         g->n_up = n - g->ubase;
         // the two sweeps' lists are independent host work (~0.1 s each at 1M
         // nodes): the down-sweep's is built on a second thread meanwhile
-        g->leaf_fm = g->fmb == 4 && env_on("CPD_LEAFFM");
+        g->leaf_fm = g->fmb == 4 && switches().leaffm;
         std::vector<uint32_t> dnodes, doff, darcs, dup;
         std::exception_ptr derr;
         std::thread dthr([&] {
@@ -1156,7 +1121,7 @@ int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
         g->asc_off.upload(off.data(), off.size(), s);
         g->asc_arcs.upload(arcs.data(), arcs.size(), s);
         HIP_CHECK(hipStreamSynchronize(s));
-        if (trace_on()) std::fprintf(stderr, "[cpd] graph up lists %.3f s\n", now_seconds() - tg0);
+        if (switches().trace) std::fprintf(stderr, "[cpd] graph up lists %.3f s\n", now_seconds() - tg0);
         g->ch_arcs = arcs.size() / 2;
         // leaf first moves in the down-sweep: 4-bit sets only (<= 4 slots)
         dthr.join();
@@ -1207,9 +1172,9 @@ int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
             g->dsc_desc.upload(desc.data(), desc.size(), s);
         }
         HIP_CHECK(hipStreamSynchronize(s));
-        if (trace_on()) std::fprintf(stderr, "[cpd] graph down lists+desc %.3f s\n", now_seconds() - tg0);
+        if (switches().trace) std::fprintf(stderr, "[cpd] graph down lists+desc %.3f s\n", now_seconds() - tg0);
         g->ch_arcs += arcs.size() / 2;
-        g->narrow = env_on("CPD_NARROW") && p->dist_bound < 0xFFFFFFFEull;
+        g->narrow = narrow_rows_on() && p->dist_bound < 0xFFFFFFFEull;
         {
             std::vector<uint32_t> lb(g->npad / 32u, 0u);
             g->dsc_lvl_leaves.assign(g->dsc_lvl.size(), 0.0);
@@ -1235,11 +1200,9 @@ int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
             return v;
         };
         {
-            // up levels of at most kNarrow nodes run chunked (CPD_UP_NARROW: A/B)
-            static const uint32_t kNarrow = [] {
-                const char* e = std::getenv("CPD_UP_NARROW");
-                return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : 1024u;
-            }();
+            // up levels of at most kNarrow nodes run chunked (256 / 1024 / 4096:
+            // 341.1k / 341.2k / 333.8k rows/s, profiles/narrow_ab/)
+            constexpr uint32_t kNarrow = 1024u;
             const uint32_t C = sweep_chunk_arcs();
             std::vector<uint32_t> items, slots;
             g->up_item_first.assign(g->asc_lvl.size(), 0);
@@ -1263,7 +1226,7 @@ int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
         g->asc_lvl_of.upload(la.data(), n, s);
         g->dsc_lvl_of.upload(ld.data(), n, s);
         HIP_CHECK(hipStreamSynchronize(s));
-        if (trace_on()) std::fprintf(stderr, "[cpd] graph levels %.3f s\n", now_seconds() - tg0);
+        if (switches().trace) std::fprintf(stderr, "[cpd] graph levels %.3f s\n", now_seconds() - tg0);
         *out = g.release();
     });
 }
@@ -1295,7 +1258,7 @@ int cpd_graph_set_coords(cpd_graph* g, const int32_t* x, const int32_t* y) {
             return;
         }
         g->lane_key = hilbert_keys(x, y, g->n);
-        if (seg_order_on()) {
+        if (switches().fm_order) {
             // first_moves gathers each column's out-neighbours' rows: with the
             // segments handed out in Hilbert order, the blocks one XCD runs at
             // once cover a compact patch of the graph and gather overlapping
@@ -1338,21 +1301,6 @@ void cpd_graph_free(cpd_graph* g) { delete g; }
 
 namespace {
 
-// CPD_LIVE=0: no up-sweep row skipping; CPD_SORT=0: batches keep the caller's
-// target order (A/B measurements; results are identical either way).
-bool live_on() {
-    static const bool on = env_on("CPD_LIVE");
-    return on;
-}
-bool lane_key_on() {  // CPD_LANE_KEY=0: ignore cpd_graph_set_coords (A/B)
-    static const bool on = env_on("CPD_LANE_KEY");
-    return on;
-}
-bool seg_order_on() {  // CPD_FM_ORDER=0: first_moves takes segments in column order (A/B)
-    static const bool on = env_on("CPD_FM_ORDER");
-    return on;
-}
-
 // Hilbert-curve index of each node's (x, y), scaled to a 2^16 x 2^16 grid over
 // the bounding box: nearby keys are nearby points, and any run of keys covers
 // a compact region (the DFS column order follows the DFS tree, whose long
@@ -1384,20 +1332,6 @@ std::vector<uint32_t> hilbert_keys(const int32_t* x, const int32_t* y, uint32_t 
     return key;
 }
 
-bool sort_on() {
-    static const bool on = env_on("CPD_SORT");
-    return on;
-}
-bool async_on() {  // CPD_ASYNC=0: every emit finishes before its batch returns
-    static const bool on = env_on("CPD_ASYNC");
-    return on;
-}
-
-
-// Distances + first-move sets for `k` targets (columns already in g->tgt,
-// padded to a multiple of 1024 with valid columns).
-bool trace_on();
-
 // After a full narrow batch (g->ovf_h = its wide group rows): switch narrow
 // rows off for good when most group rows had to be kept wide — the dense
 // final rows replace the narrow rows and the pool (nothing may still read
@@ -1408,7 +1342,7 @@ bool narrow_decide(cpd_graph* g) {
     g->narrow = false;
     g->narrow_probe = 0;
     g->alloc_final_rows();
-    if (trace_on())
+    if (switches().trace)
         std::fprintf(stderr, "[cpd] narrow rows off: %u of %llu group rows wide\n", g->ovf_h(),
                      (unsigned long long)groups);
     return true;
@@ -1426,7 +1360,7 @@ void launch_up(cpd_graph* g, uint32_t k, uint32_t slot, hipStream_t st) {
     const uint32_t active = slabs * 1024u;
     uint32_t* up = g->upx[slot].p;
     uint32_t* tmask = g->tmaskx[slot].p;
-    uint32_t* live = live_on() ? g->livex[slot].p : nullptr;
+    uint32_t* live = switches().live ? g->livex[slot].p : nullptr;
     unsigned int* stat = g->timing ? S.stat.p : nullptr;
     const size_t nasc = g->asc_lvl.size();
     S.up_late.clear();
@@ -1512,7 +1446,7 @@ void launch_down(cpd_graph* g, uint32_t k, bool narrow, uint32_t slot) {
     const double drow = narrow ? 2.0 + 4.0 / 256.0 : 4.0;
     const uint32_t slabs = (k + 1023u) / 1024u;  // active 1024-target slabs
     const uint32_t active = slabs * 1024u;
-    uint32_t* live = live_on() ? g->livex[slot].p : nullptr;
+    uint32_t* live = switches().live ? g->livex[slot].p : nullptr;
     unsigned int* stat = g->timing ? S.stat.p : nullptr;
     const size_t nasc = g->asc_lvl.size();
     cpd_graph::LateRec rec;
@@ -1613,14 +1547,14 @@ void prepare_targets(cpd_graph* g, const uint32_t* targets, uint32_t k, uint32_t
                     "target " + std::to_string(targets[i]) + " out of range");
         idx[i] = i;
     }
-    if (sort_on() && k > 0) {
+    if (switches().sort && k > 0) {
         // lanes by (Hilbert key, column), or by column without coordinates:
         // compact 2-D groups — a 256-lane group spans a small square, so its
         // final distances fit the narrow rows' 16-bit offsets (column order:
         // 5.5% of group rows wide on the 1M-node bench batch).
         // A stable LSD radix sort of the 64-bit keys (a comparison sort of a
         // 16k batch took ~1.7 ms of host time between two batches' kernels).
-        const bool hk = !g->lane_key.empty() && lane_key_on();
+        const bool hk = !g->lane_key.empty() && switches().lane_key;
         std::vector<uint64_t> kv(k), kt(k);
         std::vector<uint32_t> it(k);
         for (uint32_t i = 0; i < k; ++i)
@@ -1659,22 +1593,6 @@ void upload_targets(cpd_graph* g, const uint32_t* targets, uint32_t k, uint32_t 
                              hipMemcpyHostToDevice, st));
 }
 
-
-// CPD_OVERLAP=0: no early up-sweep of the next batch (A/B; identical rows).
-bool overlap_on() {
-    static const bool on = env_on("CPD_OVERLAP");
-    return on;
-}
-
-// CPD_TRACE=1: host-side phase times of every batch on stderr.
-bool trace_on() {
-    static const bool on = [] {
-        const char* e = std::getenv("CPD_TRACE");
-        return e && *e && *e != '0';
-    }();
-    return on;
-}
-
 // Build rows for one batch of k <= B targets; append to r (device).  next /
 // next_k (may be null / 0): the targets of the batch that follows; its
 // up-sweep is queued first, on ustream behind this batch's own: it writes
@@ -1708,7 +1626,7 @@ void build_batch(cpd_graph* g, const uint32_t* targets, uint32_t k, cpd_rows* r,
     // it runs beside the previous batch's first moves, ahead of this
     // down-sweep, which the host's launch latency then never delays.
     const uint32_t ns = slot ^ 1u;
-    if (next && next_k && overlap_on()) {
+    if (next && next_k && switches().overlap) {
         prepare_targets(g, next, next_k, ns);
         // after the other slot's last batch: its down-sweep (ev_down, not yet
         // re-recorded for this batch), so this up-sweep runs beside its first
@@ -1764,7 +1682,7 @@ void build_batch(cpd_graph* g, const uint32_t* targets, uint32_t k, cpd_rows* r,
         HIP_CHECK(hipStreamSynchronize(g->stream));
         g->drop_prep();
         if (g->timing) g->agg["pool_rebuilds"].launches += 1;
-        if (trace_on())
+        if (switches().trace)
             std::fprintf(stderr, "[cpd] batch of %u rows: %u wide group rows past the pool's %u, rebuilt\n",
                          k, g->ovf_h(), g->pool_cap);
         const uint32_t piece =
@@ -1800,7 +1718,7 @@ void build_batch(cpd_graph* g, const uint32_t* targets, uint32_t k, cpd_rows* r,
         const uint32_t nch = g->fmb == 4 ? rle_count_chunks(npad) : 0u;
         if (rle_fused(g->fmb)) {
             // one pass: each set read once, the tables written, the run counts
-            // summed from the chunks (rle_emit4 + the seam check rle_emit_fix)
+            // summed from the chunks (rle_emit8 + the seam check rle_emit_fix)
             const uint32_t ec = rle_emit_chunks(npad);
             const size_t cks = (size_t)k * ec;
             g->timed("rle_emit", (fm_row + 4.0 * r->wpr) * k + 24.0 * cks + 8.0 * k, [&] {
@@ -1851,7 +1769,7 @@ void build_batch(cpd_graph* g, const uint32_t* targets, uint32_t k, cpd_rows* r,
     emit();
     // the previous batch's sweep bytes: its stats landed before this down-sweep
     if (g->timing) fold_late(g, 1);
-    if (trace_on())
+    if (switches().trace)
         std::fprintf(stderr, "[cpd] batch %u rows: launch sweeps+fm %.2f ms, to down-sweep end %.2f "
                              "ms, count+emit queued %.2f ms\n",
                      k, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (now_seconds() - t2) * 1e3);
@@ -2689,19 +2607,19 @@ int cpd_query_run(cpd_index* ix, int32_t k_moves, cpd_query_stats* st) {
         const uint32_t* adj = ix->custom_w ? ix->adj_sel.p : g->adj.p;
         (void)hipGetLastError();
         if (nq && dense)
-            launch_table_search_dense(adj, g->adj_shift, ix->d_row_of_col.p, ix->dense.p, g->npad, g->tlb,
-                                      ix->qs.p, ix->qt.p, ix->qrow.p, nq, k_moves, g->n,
-                                      ix->cost.p, ix->hops.p, ix->fin.p, ix->agg.p, g->stream);
+            launch_table_search_dense(adj, g->adj_shift, ix->dense.p, g->npad, g->tlb, ix->qs.p,
+                                      ix->qt.p, ix->qrow.p, nq, k_moves, g->n, ix->cost.p,
+                                      ix->hops.p, ix->fin.p, ix->agg.p, g->stream);
         else if (nq)
-            launch_table_search(adj, g->adj_shift, ix->d_row_of_col.p, ix->off.p, ix->runs.p,
-                                ix->qs.p, ix->qt.p, ix->qrow.p, nq, k_moves, g->n, ix->cost.p,
-                                ix->hops.p, ix->fin.p, ix->agg.p, g->stream);
+            launch_table_search(adj, g->adj_shift, ix->off.p, ix->runs.p, ix->qs.p, ix->qt.p,
+                                ix->qrow.p, nq, k_moves, g->n, ix->cost.p, ix->hops.p,
+                                ix->fin.p, ix->agg.p, g->stream);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(b, g->stream));
         unsigned long long hagg[4] = {0, 0, 0, 0};
         HIP_CHECK(hipMemcpyAsync(hagg, ix->agg.p, sizeof hagg, hipMemcpyDeviceToHost, g->stream));
         HIP_CHECK(hipStreamSynchronize(g->stream));
-        if (hagg[3] && search_trace())  // CPD_TS_SHARE: the moves suffix sharing skipped
+        if (hagg[3] && switches().search_trace)
             std::fprintf(stderr, "[walk] %llu queries, %llu moves, %llu of them taken from "
                          "earlier walks' suffixes\n", (unsigned long long)nq, hagg[1], hagg[3]);
         float ms = 0.f;
@@ -2808,14 +2726,6 @@ uint32_t pow2_at_least(uint64_t x) {
     uint32_t c = 64;
     while (c < x && c < (1u << 24)) c <<= 1;
     return c;
-}
-
-bool search_trace() {
-    static const bool on = [] {
-        const char* e = std::getenv("CPD_SEARCH_TRACE");
-        return e && *e && *e != '0';
-    }();
-    return on;
 }
 
 }  // namespace
@@ -2975,11 +2885,7 @@ int cpd_query_search(cpd_index* ix, const cpd_search_opts* opts, cpd_search_stat
             if (more) {
                 const uint64_t want = (uint64_t)m * search_spill_words(cap, tables);
                 const uint64_t left = share > (size_t)slots * per_slot ? share - (size_t)slots * per_slot : 0;
-                uint64_t words = std::min<uint64_t>(want, left / 4u);
-                // CPD_SEARCH_POOL_WORDS (tests): a smaller pool, so that some
-                // records find it full and their searches restart instead
-                if (const char* e = std::getenv("CPD_SEARCH_POOL_WORDS"))
-                    if (*e) words = std::min<uint64_t>(words, std::strtoull(e, nullptr, 10));
+                const uint64_t words = search_pool_words(std::min<uint64_t>(want, left / 4u));
                 if (words >= search_spill_words(cap, tables)) {
                     DevBuf<uint32_t>& out = ix->spool[pin ^ 1];
                     out.release();
@@ -3020,7 +2926,7 @@ int cpd_query_search(cpd_index* ix, const cpd_search_opts* opts, cpd_search_stat
             for (int k = 0; k < 7; ++k) h[k] += hp[k];
             h[7] = hp[7];
             cap_last = cap;
-            if (search_trace())
+            if (switches().search_trace)
                 std::fprintf(stderr, "[cpd_search] pass %u: %u queries, capacity %u, %u lanes, "
                              "%.3f ms, %llu expanded, %llu overflowed, pool %llu words\n",
                              passes, m, cap, slots, pms, (unsigned long long)hp[0],

@@ -16,9 +16,9 @@
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 
 #include "cpd_kernels.hpp"
+#include "cpd_switches.hpp"
 
 namespace cpd {
 namespace kern {
@@ -400,23 +400,6 @@ __device__ __forceinline__ void narrow_store8(const NarrowRows& nr, uint32_t col
     const uint4 q = make_uint4(q0 | (q1 << 16), q2 | (q3 << 16), q4 | (q5 << 16), q6 | (q7 << 16));
     reinterpret_cast<uint4*>(nr.d16)[(size_t)col * B8 + l8] = q;
     if (head) nr.base[(size_t)grp * nr.n + col] = b;
-}
-
-__device__ __forceinline__ void fm_nib(const uint4& dv, const uint4& acc, uint32_t w, int k,
-                                       uint32_t (&bits)[4]) {
-    bits[0] |= (sat_add(dv.x, w) == acc.x ? 1u : 0u) << k;
-    bits[1] |= (sat_add(dv.y, w) == acc.y ? 1u : 0u) << k;
-    bits[2] |= (sat_add(dv.z, w) == acc.z ? 1u : 0u) << k;
-    bits[3] |= (sat_add(dv.w, w) == acc.w ? 1u : 0u) << k;
-}
-
-__device__ __forceinline__ uint32_t fm_pack4(const uint4& t, const uint4& acc, uint32_t v,
-                                             const uint32_t (&bits)[4]) {
-    const uint32_t b0 = (t.x == v || acc.x == INF) ? 0xFu : bits[0];  // wildcard (target, unreachable)
-    const uint32_t b1 = (t.y == v || acc.y == INF) ? 0xFu : bits[1];
-    const uint32_t b2 = (t.z == v || acc.z == INF) ? 0xFu : bits[2];
-    const uint32_t b3 = (t.w == v || acc.w == INF) ? 0xFu : bits[3];
-    return b0 | (b1 << 4) | (b2 << 8) | (b3 << 12);
 }
 
 // Leaf slot of the narrow down-sweep: d(v) = min over the out-edges (all to
@@ -993,7 +976,7 @@ __global__ __launch_bounds__(256) void first_moves(const uint2* __restrict__ adj
 // self loop adds w + d(c) >= d(c) and so never lowers the minimum), all of
 // them final here, and d(c) == INF exactly when every term is INF — so the
 // sets {k : w_k + d(v_k) == d(c)} follow from the neighbour rows alone,
-// bit-identical, one gather per column fewer.  (Reading it, CPD_FM_OWN in
+// bit-identical, one gather per column fewer.  (Reading it, a switch of
 // round 2, was slower and is gone.)
 template <int G>
 struct FmGroup {  // edges are re-read from the lanes when needed (no SGPR pressure)
@@ -1009,7 +992,7 @@ struct FmGroup {  // edges are re-read from the lanes when needed (no SGPR press
 // 8.8 GB per launch: L2 does not merge them) and 24.4 vs 12.6 ms.  Columns
 // are gathered G = 2 at a time, the next group issued before the current one
 // is finished (G = 1 measured 16.2 against 15.3 ms; two segments per
-// workgroup, CPD_FM_SEGS = 2, 101 VGPRs and slower: both removed in round 3).
+// workgroup side by side, 101 VGPRs and slower: both removed in round 3).
 // Held to 64 VGPRs for 8 waves per SIMD (round 6: 65 VGPRs had given 7; the
 // cap spills 7 rarely-used values to scratch): 22.8-23.0 against 26.6-26.8
 // ms beside the up-sweep, 429.9-430.2k against 419.7-420.8k rows/s
@@ -1393,28 +1376,6 @@ __device__ __forceinline__ void store_cols32_wave(uint32_t* __restrict__ row, ui
         const uint32_t w2 = (uint32_t)__shfl_down((int)w, 2, 64);
         const uint32_t w3 = (uint32_t)__shfl_down((int)w, 3, 64);
         if (!(lane & 3u)) reinterpret_cast<uint4*>(row)[g >> 2] = make_uint4(w, w1, w2, w3);
-    }
-}
-__device__ __forceinline__ void load_cols32(const uint32_t* __restrict__ row, uint32_t g, uint32_t lb,
-                                            uint32_t (&x)[4]) {
-    if (lb == 2u) {
-        const uint4 q = reinterpret_cast<const uint4*>(row)[g];
-        x[0] = q.x;
-        x[1] = q.y;
-        x[2] = q.z;
-        x[3] = q.w;
-    } else if (lb == 1u) {
-        const uint2 q = reinterpret_cast<const uint2*>(row)[g];
-        x[0] = nib_from2(q.x);
-        x[1] = nib_from2(q.x >> 16);
-        x[2] = nib_from2(q.y);
-        x[3] = nib_from2(q.y >> 16);
-    } else {
-        const uint32_t q = row[g];
-        x[0] = nib_from1(q);
-        x[1] = nib_from1(q >> 8);
-        x[2] = nib_from1(q >> 16);
-        x[3] = nib_from1(q >> 24);
     }
 }
 
@@ -1947,8 +1908,8 @@ __global__ __launch_bounds__(64) void rle_emit_fix(const uint32_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
-// The fused emit, eight rows per wave (round 6).  rle_emit4's wave scanned
-// one row, so each greedy step moved one 4-bit set: ~17 VALU instructions
+// The fused emit, eight rows per wave (round 6).  Round 5's emit scanned one
+// row per wave, so each greedy step moved one 4-bit set: ~17 VALU instructions
 // per (row, column), and the emit, ALU-bound, took 15 ms of every step's
 // CUs.  Here a lane holds one COLUMN of eight rows per 32-bit word (nibble i
 // = row 8·oct + i; the 64-B sectors of the two row groups transposed in
@@ -1979,7 +1940,7 @@ __global__ __launch_bounds__(64) void rle_emit_fix(const uint32_t* __restrict__ 
 //            the table's 1/2/4-bit fields and transposed back to rows: one
 //            4-, 8- or 16-B store per row and lane, a wave writing 256 B-1
 //            KiB contiguous per row.
-// It records per (row, chunk) what round 5's one-row rle_emit4 recorded
+// It records per (row, chunk) what round 5's one-row emit recorded
 // (guessed entry, exit, breaks), so rle_emit_fix repairs a wrong chunk guess
 // with emit_chunk4, the one-row form, as before.
 __device__ __forceinline__ uint32_t zero_nib(uint32_t a) {  // bit 3 of nibble k: nibble k is 0
@@ -2406,9 +2367,9 @@ __global__ __launch_bounds__(256) void moves_runs(const uint32_t* __restrict__ d
 }
 
 // ---------------------------------------------------------------------------
-// RLE count, chunked (4-bit sets; CPD_RLE_CH, default on).  rle_scan<false>
-// gives each lane one 32-column segment of a 2048-column tile and guesses
-// the state entering it (16 look-back columns), then rescans every segment
+// RLE count, chunked (4-bit sets on the unfused path, CPD_RLE_FUSED=0;
+// unconditional there).  rle_scan gives each lane one 32-column segment of
+// a 2048-column tile and guesses the state entering it (16 look-back columns), then rescans every segment
 // whose guess was wrong — and a wave pays a whole rescan whenever any of
 // its 64 lanes needs one — about 80 column steps per 32 useful ones.  Here a
 // lane owns a chunk of CH consecutive segments of one row and scans them in
@@ -2528,7 +2489,7 @@ __global__ __launch_bounds__(256) void rle_count_ch(const uint32_t* __restrict__
 // A row whose rescans pass kFixBudget segments (runs far longer than the
 // look-back — never on road graphs, where a run averages 1.6 columns, but a
 // chain graph has a handful of runs per row) is given up: *hard = 1, and the
-// host re-counts the batch with rle_scan<false>, which bounds that case.
+// host re-counts the batch with rle_scan, which bounds that case.
 constexpr uint32_t kFixBudget = 256;  // segments rescanned per row
 
 template <int CH>
@@ -4138,43 +4099,16 @@ void set_launch_events(hipEvent_t start, hipEvent_t stop) {
     g_ev_stop = stop;
 }
 
-// CPD_XCD=0 turns the XCD-aware block remap off (A/B measurements).
-uint32_t xcd_remap() {
-    static const uint32_t on = [] {
-        const char* e = std::getenv("CPD_XCD");
-        return (e && *e == '0') ? 0u : 1u;
-    }();
-    return on;
-}
+// the XCD-aware block remap as the kernels take it (CPD_XCD=0: off)
+static uint32_t xcd_remap() { return switches().xcd ? 1u : 0u; }
 
-// Tuning knobs for A/B runs: waves per workgroup of the down-sweep and of
-// first_moves (CPD_DOWN_WPB, CPD_FM_WPB: 1, 2 or 4; a workgroup covers
-// 256 x wpb targets), columns per gather group of first_moves (CPD_FM_G).
-// Defaults = the fastest measured on the 1M-node bench (MI355X, 16k rows):
-// down 4 waves (1: +5 %, 2: +8 %), first_moves 2 waves (4: +11 %), G = 2
-// (1: +4 %, 4: +14 %).
-uint32_t env_u32(const char* name, uint32_t dflt) {
-    const char* e = std::getenv(name);
-    return (e && *e) ? (uint32_t)std::strtoul(e, nullptr, 10) : dflt;
-}
-uint32_t down_wpb() {
-    static const uint32_t v = env_u32("CPD_DOWN_WPB", 4);
-    return v;
-}
-uint32_t down8_wpb() {  // CPD_DOWN8_WPB: 1, 2 or 4 waves per narrow down-sweep workgroup
-    static const uint32_t v = [] {
-        const uint32_t w = env_u32("CPD_DOWN8_WPB", 2);
-        return w == 1 ? 1u : (w == 4 ? 4u : 2u);
-    }();
-    return v;
-}
-uint32_t fm_wpb() {
-    static const uint32_t v = env_u32("CPD_FM_WPB", 2);
-    return v;
-}
-// narrow rows, 4-slot adjacency: first_moves_n4 (the generic
-// first_moves<4, 2, true> measured slower and is not launched)
-uint32_t fm_n4() { return 1u; }
+// Waves per workgroup of the down-sweep (kDownWpb), of the narrow down-sweep
+// (kDown8Wpb) and of first_moves (kFmWpb); a workgroup covers 256 x waves
+// targets, 512 x waves in the narrow down-sweep.  The fastest measured on the
+// 1M-node bench (MI355X, 16k rows): down 4 waves (1: +5 %, 2: +8 %),
+// first_moves 2 waves (4: +11 %) with 2 columns per gather group, the G of
+// first_moves<4, 2, *> (1: +4 %, 4: +14 %).
+constexpr uint32_t kDownWpb = 4, kDown8Wpb = 2, kFmWpb = 2;
 
 void launch_sweep(bool ascend, const uint32_t* nodes, const uint32_t* arc_off,
                   const uint32_t* arcs32, uint32_t slot0, uint32_t count, uint32_t* dist,
@@ -4198,15 +4132,12 @@ void launch_sweep(bool ascend, const uint32_t* nodes, const uint32_t* arc_off,
                slot0, count, xcd_remap(), dist, up, ubase, uidx, t4, B / 4u, cf,
                (const uint32_t*)nullptr, lf);
     } else {
-        const uint32_t tpb = 64u * down_wpb();  // a workgroup covers 4 * tpb targets
+        constexpr uint32_t tpb = 64u * kDownWpb;  // a workgroup covers 4 * tpb targets
         const dim3 grid(count * slabs * (256u / tpb)), blk(tpb);
         if (nr.d16) {
-            // 8 targets per lane: a workgroup of 64 x wpb8 lanes covers 512 x wpb8
-            // targets (wpb8 = 2: one 1024-target slab)
-            // (4 waves = 2048 targets: only when the slab count is even)
-            const uint32_t wpb8 = down8_wpb() == 4 && slabs % 2 ? 2u : down8_wpb();
-            const uint32_t tpb8 = 64u * wpb8;
-            const dim3 g8(count * slabs * 2u / wpb8), b8(tpb8);
+            // 8 targets per lane: a workgroup of 64 x kDown8Wpb lanes covers
+            // 512 x kDown8Wpb targets (2 waves: one 1024-target slab)
+            const dim3 g8(count * slabs * 2u / kDown8Wpb), b8(64u * kDown8Wpb);
             launch(kern::sweep_down8, g8, b8, s, reinterpret_cast<const uint4*>(desc), arcs, slot0,
                    count, xcd_remap(), (const uint32_t*)up, t4, B / 4u, cf, (const uint32_t*)live,
                    fmleaf, nr);
@@ -4216,15 +4147,14 @@ void launch_sweep(bool ascend, const uint32_t* nodes, const uint32_t* arc_off,
     }
 }
 
-static uint32_t up_init_blocks() { return 2048u; }  // the init's grid (grid-stride, one wave each)
-
 void launch_sweep_up_init(const uint32_t* slots, uint32_t nslots, const uint32_t* nodes,
                           uint32_t* up, uint32_t ubase, const uint32_t* tgt, uint32_t B,
                           uint32_t slabs, uint32_t* live, const uint32_t* tmask, hipStream_t s) {
     if (!nslots) return;
     const uint32_t active = slabs >= 32 ? 0xFFFFFFFFu : ((1u << slabs) - 1u);
     const uint32_t total = nslots * slabs * kern::kUpQ;
-    launch(kern::sweep_up_init, dim3(std::min(total, up_init_blocks())), dim3(64), s, slots,
+    constexpr uint32_t kBlocks = 2048u;  // the init's grid (grid-stride, one wave each)
+    launch(kern::sweep_up_init, dim3(std::min(total, kBlocks)), dim3(64), s, slots,
            nslots, total, nodes, up, ubase, reinterpret_cast<const uint4*>(tgt), B / 4u, live,
            tmask, active);
 }
@@ -4266,20 +4196,13 @@ void launch_live_stats(bool ascend, const uint32_t* nodes, const uint32_t* arc_o
                slot1, ubase, uidx, live, stat);
 }
 
-// segments per first_moves_n4 workgroup, one after another (CPD_FM_SPW: 1,
-// 2, 4, ..., 64).  At 7 waves per SIMD 8 measured 418.6-423.4k rows/s
+// Segments per first_moves_n4 workgroup, one after another (a power of 2, at
+// most 64).  At 7 waves per SIMD 8 measured 418.6-423.4k rows/s
 // against 413.2-419.1k for one (profiles/up_store_ab/r06n_*, r06o_*); at 8
 // waves per SIMD, whose workgroups hold every slot the up-sweep beside them
 // needs, shorter workgroups hand slots over sooner: 2 measured 440.5-441.2k
 // against 435.3-435.4k for 8 and 435.7-436.0k for 1 (r06ee_*)
-static uint32_t fm_spw() {
-    static const uint32_t v = [] {
-        const char* e = std::getenv("CPD_FM_SPW");
-        const uint32_t x = e && *e ? (uint32_t)std::atoi(e) : 2u;
-        return (x && x <= 64u && !(x & (x - 1u))) ? x : 1u;
-    }();
-    return v;
-}
+constexpr uint32_t kFmSpw = 2;
 
 uint32_t fm_bits(uint32_t shift) { return shift <= 2 ? 4u : (1u << shift); }
 
@@ -4292,7 +4215,9 @@ static void launch_first_moves_t(const uint2* adj, uint32_t shift, const uint32_
     switch (shift) {  // SLOTS = 2^shift edges per column; G columns per gather group
         case 0: launch(kern::first_moves<1, 4, NARROW>, grid, blk, s, adj, dist, tgt, B, n, npad, r, fm, leafbits, fmleaf, nr); break;
         case 1: launch(kern::first_moves<2, 2, NARROW>, grid, blk, s, adj, dist, tgt, B, n, npad, r, fm, leafbits, fmleaf, nr); break;
-        case 2: launch(kern::first_moves<4, 2, NARROW>, grid, blk, s, adj, dist, tgt, B, n, npad, r, fm, leafbits, fmleaf, nr); break;
+        case 2:  // narrow rows: first_moves_n4 instead (launch_first_moves)
+            if constexpr (!NARROW) launch(kern::first_moves<4, 2, false>, grid, blk, s, adj, dist, tgt, B, n, npad, r, fm, leafbits, fmleaf, nr);
+            break;
         case 3: launch(kern::first_moves<8, 1, NARROW>, grid, blk, s, adj, dist, tgt, B, n, npad, r, fm, leafbits, fmleaf, nr); break;
         default: launch(kern::first_moves<16, 1, NARROW>, grid, blk, s, adj, dist, tgt, B, n, npad, r, fm, leafbits, fmleaf, nr); break;
     }
@@ -4303,14 +4228,13 @@ void launch_first_moves(const uint32_t* adj32, uint32_t shift, const uint32_t* d
                         uint32_t npad, uint32_t* fm, const uint32_t* leafbits,
                         const uint16_t* fmleaf, NarrowRows nr, hipStream_t s,
                         const uint32_t* seg_order) {
-    const uint32_t tpb = 64u * fm_wpb();  // a workgroup covers 4 * tpb targets
+    constexpr uint32_t tpb = 64u * kFmWpb;  // a workgroup covers 4 * tpb targets
     const dim3 grid((npad / kern::kSeg) * ((rows + 1023u) / 1024u) * (256u / tpb)), blk(tpb);
     const uint2* adj = reinterpret_cast<const uint2*>(adj32);
-    if (nr.d16 && shift == 2 && fm_n4()) {
-        const uint32_t spw = fm_spw();
-        launch_shm(kern::first_moves_n4<2>, dim3(grid.x / spw), blk, 64u * tpb, s, adj, dist, tgt,
-                   B, n, npad, xcd_remap(), fm, leafbits, fmleaf, nr, seg_order, spw);
-    } else if (nr.d16)
+    if (nr.d16 && shift == 2)  // the generic first_moves<4, 2, true> measured slower
+        launch_shm(kern::first_moves_n4<2>, dim3(grid.x / kFmSpw), blk, 64u * tpb, s, adj, dist,
+                   tgt, B, n, npad, xcd_remap(), fm, leafbits, fmleaf, nr, seg_order, kFmSpw);
+    else if (nr.d16)
         launch_first_moves_t<true>(adj, shift, dist, tgt, B, n, npad, fm, leafbits, fmleaf, nr,
                                    grid, blk, s);
     else
@@ -4319,7 +4243,7 @@ void launch_first_moves(const uint32_t* adj32, uint32_t shift, const uint32_t* d
 }
 
 bool first_moves_reads_own(uint32_t shift, bool narrow) {
-    return !(narrow && shift == 2 && fm_n4());  // only the generic kernel reads it
+    return !(narrow && shift == 2);  // first_moves_n4 does not, the generic kernel does
 }
 
 void launch_rle_count(const uint32_t* fm, uint32_t fmb, uint32_t npad, uint32_t nrows,
@@ -4436,37 +4360,30 @@ void launch_expand_rows(const uint64_t* offsets, const uint32_t* runs, const uin
 }
 
 // Table-search chunking (launch parameters only; results are identical under
-// every setting): the batch is cut into chunks of ceil(nq / waves) queries (a
-// multiple of 64, at most 1024 for dense rows), CPD_TS_WAVES
-// overriding the wave count.  Measured on the 1M-node bench (1M queries,
+// every setting): the batch is cut into chunks of ceil(nq / waves_target)
+// queries (a multiple of 64, at most 1024 for dense rows), waves_target =
+// kDenseWaves or kRleWaves.  Measured on the 1M-node bench (1M queries,
 // MI355X, tools_scripts/query_ab.py): dense walks want few waves that each
 // refill their lanes ~16 times (waves 1024: 88M q/s; 8192 waves, i.e. no
 // refill: 60M; round 1's lane per query: 43.7M), RLE walks — a chain of
 // dependent loads per hop — want every wave slot filled (8192).  Two walks
 // per lane (ILP 2) was slower in both forms; it and round 1's lane-per-query
 // kernels were removed in round 3.
-uint32_t ts_waves(uint32_t dflt) {
-    static const uint32_t v = env_u32("CPD_TS_WAVES", 0);
-    return v ? v : dflt;
-}
+// Waves per workgroup: dense walks 1 (their ~1000 waves spread over every
+// CU: 92.3M against 90.3M q/s with 4), RLE walks 4 (8192 one-wave workgroups
+// ran out of workgroup slots: 8.2M against 11.4M; profiles/walk_wpb_ab/).
+constexpr uint32_t kDenseWaves = 1024, kDenseWpb = 1, kRleWaves = 8192, kRleWpb = 4;
 
 template <class Rows>
 static void launch_walk(const uint2* adj, uint32_t shift, const Rows& rows, const uint32_t* qs,
                         const uint32_t* qt, const uint32_t* qrow, uint32_t nq, uint32_t limit,
                         uint64_t* cost, uint32_t* hops, uint8_t* fin, unsigned long long* agg,
-                        uint32_t waves_target, uint32_t chunk_max, hipStream_t s,
-                        uint32_t wpb_default) {
+                        uint32_t waves_target, uint32_t chunk_max, hipStream_t s, uint32_t wpb) {
     constexpr uint32_t unit = 64u;
     uint64_t chunk = ((uint64_t)nq + waves_target - 1u) / waves_target;
     chunk = std::min<uint64_t>(chunk, std::max(unit, chunk_max));
     chunk = std::max<uint64_t>(unit, (chunk + unit - 1u) / unit * unit);
     const uint64_t waves = ((uint64_t)nq + chunk - 1u) / chunk;
-    // waves per workgroup: dense walks 1 (their ~1000 waves spread over every
-    // CU: 92.3M against 90.3M q/s with 4), RLE walks 4 (8192 one-wave
-    // workgroups ran out of workgroup slots: 8.2M against 11.4M);
-    // CPD_TS_WPB overrides both (A/B, profiles/walk_wpb_ab/)
-    static const uint32_t wpb_env = env_u32("CPD_TS_WPB", 0);
-    const uint32_t wpb = std::min(4u, std::max(1u, wpb_env ? wpb_env : wpb_default));
     const dim3 grid((uint32_t)std::max<uint64_t>(1u, (waves + wpb - 1u) / wpb)), blk(64u * wpb);
     const uint32_t c = (uint32_t)chunk;
 #define CPD_WALK(SH, IL)                                                                       \
@@ -4486,36 +4403,34 @@ static uint32_t walk_limit(int32_t kmoves, uint32_t n) {
     return kmoves >= 0 ? std::min((uint32_t)kmoves, n) : n;
 }
 
-void launch_table_search_dense(const uint32_t* adj, uint32_t shift, const uint32_t* row_of_col,
-                               const uint32_t* dense, uint32_t npad, uint32_t lb,
-                               const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
-                               uint32_t nq, int32_t kmoves, uint32_t n, uint64_t* cost,
-                               uint32_t* hops, uint8_t* fin, unsigned long long* agg,
-                               hipStream_t s) {
+void launch_table_search_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                               uint32_t npad, uint32_t lb, const uint32_t* qs, const uint32_t* qt,
+                               const uint32_t* qrow, uint32_t nq, int32_t kmoves, uint32_t n,
+                               uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                               unsigned long long* agg, hipStream_t s) {
     const kern::DenseRows rows{dense, npad >> (5u - lb), kern::Tbl{lb}};
     launch_walk(reinterpret_cast<const uint2*>(adj), shift, rows, qs, qt, qrow, nq,
-                walk_limit(kmoves, n), cost, hops, fin, agg, ts_waves(1024), 1024u, s,
-                1u);
+                walk_limit(kmoves, n), cost, hops, fin, agg, kDenseWaves, 1024u, s, kDenseWpb);
 }
 
-void launch_table_search(const uint32_t* adj, uint32_t shift, const uint32_t* row_of_col,
-                         const uint64_t* offsets, const uint32_t* runs, const uint32_t* qs,
-                         const uint32_t* qt, const uint32_t* qrow, uint32_t nq, int32_t kmoves,
-                         uint32_t n, uint64_t* cost, uint32_t* hops, uint8_t* fin,
-                         unsigned long long* agg, hipStream_t s) {
+void launch_table_search(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                         const uint32_t* runs, const uint32_t* qs, const uint32_t* qt,
+                         const uint32_t* qrow, uint32_t nq, int32_t kmoves, uint32_t n,
+                         uint64_t* cost, uint32_t* hops, uint8_t* fin, unsigned long long* agg,
+                         hipStream_t s) {
     launch_walk(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs}, qs, qt,
-                qrow, nq, walk_limit(kmoves, n), cost, hops, fin, agg, ts_waves(8192),
-                1u << 30, s, 4u);
+                qrow, nq, walk_limit(kmoves, n), cost, hops, fin, agg, kRleWaves, 1u << 30, s,
+                kRleWpb);
 }
 
 
-// Lane slots for nq searches: at most CPD_SEARCH_WAVES (1024) one-wave
-// workgroups (64k lanes: 3,389 q/s at fscale 0 on the 1M graph against
-// 1,657 with 256 waves, profiles/search_lanes_ab/), a whole wave each
+// Lane slots for nq searches: at most kSearchWaves one-wave workgroups (64k
+// lanes: 3,389 q/s at fscale 0 on the 1M graph against 1,657 with 256 waves,
+// profiles/search_lanes_ab/), a whole wave each
 uint32_t search_slots(uint32_t nq) {
-    static const uint32_t waves = std::max(1u, env_u32("CPD_SEARCH_WAVES", 1024));
+    constexpr uint32_t kSearchWaves = 1024;
     const uint32_t want = (nq + 63u) / 64u;
-    return 64u * std::max(1u, std::min(waves, want));
+    return 64u * std::max(1u, std::min(kSearchWaves, want));
 }
 
 void launch_search_tables(const uint32_t* dense, uint32_t npad, uint32_t lb, const uint32_t* adj_f,
@@ -4566,16 +4481,16 @@ void launch_cpd_search(const uint32_t* adj_f, const uint32_t* adj_w, uint32_t sh
     const bool tables = hrow != nullptr;
     // Few searches left (a late pass): fewer lanes per wave, more waves —
     // each wave issues for fewer divergent lanes, and the SIMDs a full-wave
-    // launch would leave idle take the rest (CPD_SEARCH_LPW_MIN: the fewest
-    // lanes per wave allowed, default 8; 64 = off — profiles/search_heap_ab/
+    // launch would leave idle take the rest (kLpwMin: the fewest lanes per
+    // wave allowed; 64 would be whole waves always — profiles/search_heap_ab/
     // r05aj: fscale 0 5.51-5.69k against 5.03k q/s)
-    static const uint32_t lpw_min = std::max(8u, std::min(64u, env_u32("CPD_SEARCH_LPW_MIN", 8)));
+    constexpr uint32_t kLpwMin = 8;
     // (the fewest lanes, a multiple of 8, at which the slots' waves still fit
     // one per SIMD: 1024 one-wave workgroups; more waves queued behind the
     // resident ones lost their A/B in round 5, profiles/search_resident_ab/)
     constexpr uint32_t resident = 1024u;
     const uint32_t fit = (uint32_t)(((uint64_t)slots + resident - 1u) / resident);
-    const uint32_t lpw = std::max(lpw_min, std::min(64u, (fit + 7u) / 8u * 8u));
+    const uint32_t lpw = std::max(kLpwMin, std::min(64u, (fit + 7u) / 8u * 8u));
     const uint32_t waves = slots / lpw;  // waves x lpw <= slots workspaces
     kern::SearchWs w;
     w.cap = cap;

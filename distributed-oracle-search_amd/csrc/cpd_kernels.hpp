@@ -139,7 +139,7 @@ void launch_rle_count(const uint32_t* fm, uint32_t fmb, uint32_t npad, uint32_t 
 void launch_rle_moves(const uint32_t* fm, uint32_t fmb, uint32_t npad, uint32_t nrows,
                       const uint32_t* st, const uint8_t* rc, const uint32_t* out_row,
                       uint32_t lb, uint32_t* dense, hipStream_t s);
-// Count and emit fused (4-bit sets; cpd_kernels.hip rle_emit4): the move
+// Count and emit fused (4-bit sets; cpd_kernels.hip rle_emit8): the move
 // tables as launch_rle_moves writes them and counts[r] = row r's runs, each
 // set read once, no segment states; then rle_emit_fix redoes the rare chunk
 // whose guessed entry was wrong.  xe / xs / cc: nrows x rle_emit_chunks(npad)
@@ -224,21 +224,20 @@ void launch_scatter_u8(const uint8_t* in, const uint32_t* perm, uint32_t nq, uin
                        hipStream_t st);
 
 // table-search over dense move tables.  qs / qt: query columns, sorted by
-// target row; qrow[q]: the row of query q's target (row_of_col is unused).
-void launch_table_search_dense(const uint32_t* adj, uint32_t shift, const uint32_t* row_of_col,
-                               const uint32_t* dense, uint32_t npad, uint32_t lb,
-                               const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
-                               uint32_t nq, int32_t kmoves, uint32_t n, uint64_t* cost,
-                               uint32_t* hops, uint8_t* fin, unsigned long long* agg,
-                               hipStream_t s);
+// target row; qrow[q]: the row of query q's target.
+void launch_table_search_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                               uint32_t npad, uint32_t lb, const uint32_t* qs, const uint32_t* qt,
+                               const uint32_t* qrow, uint32_t nq, int32_t kmoves, uint32_t n,
+                               uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                               unsigned long long* agg, hipStream_t s);
 
 // adj: packed fixed-stride adjacency, (dst column, weight) pairs, 2^shift
 // slots per column, dst = 0xFFFFFFFF past the out-degree.
-void launch_table_search(const uint32_t* adj, uint32_t shift, const uint32_t* row_of_col,
-                         const uint64_t* offsets, const uint32_t* runs, const uint32_t* qs,
-                         const uint32_t* qt, const uint32_t* qrow, uint32_t nq, int32_t kmoves,
-                         uint32_t n, uint64_t* cost, uint32_t* hops, uint8_t* fin,
-                         unsigned long long* agg, hipStream_t s);
+void launch_table_search(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                         const uint32_t* runs, const uint32_t* qs, const uint32_t* qt,
+                         const uint32_t* qrow, uint32_t nq, int32_t kmoves, uint32_t n,
+                         uint64_t* cost, uint32_t* hops, uint8_t* fin, unsigned long long* agg,
+                         hipStream_t s);
 
 // CPD-heuristic search (cpd_kernels.hip "CPD-heuristic search"): one search
 // per query (sorted by target row, qrow as for table-search) over the dense

@@ -213,7 +213,7 @@ def test_generic_emit_matches_greedy():
 
 
 # The table-width conversions of cpd_kernels.hip (nib_to2 / nib_to1 /
-# nib_from2 / nib_from1, store_cols32 / load_cols32), restated bit for bit.
+# nib_from2 / nib_from1, store_cols32), restated bit for bit.
 M32 = 0xFFFFFFFF
 
 
@@ -259,7 +259,7 @@ def test_table_width_conversions():
             assert frm(narrow) == nib, (bits, mv)
 
 
-# The fused one-pass emit (cpd_kernels.hip rle_emit4 / emit_chunk4 /
+# The fused one-pass emit (cpd_kernels.hip rle_emit8 / emit_chunk4 /
 # rle_emit_fix), restated: per chunk of KT tiles the segments' entry sets by
 # the lanes' guesses and a fixed point, the closing set of the run open at
 # the chunk's right edge by a prefix-AND look-ahead, the backward fill of
