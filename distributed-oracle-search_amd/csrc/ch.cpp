@@ -148,10 +148,12 @@ struct Contractor {
             uint64_t via = (uint64_t)a.w + b.w;
             if (ws.get(b.v) <= via) continue;
             ++count;
-            if (outv) {
-                if (via >= 0xFFFFFFFFull) throw Error(CPD_E_RANGE, "shortcut weight >= 2^32-1");
-                outv->push_back({a.v, b.v, (uint32_t)via});
-            }
+            // A shortcut of weight >= 2^32-1 is counted (the priority is what
+            // it was) but never emitted: it is needed only if u->v->x is a
+            // shortest path, whose length is then a real distance and so at
+            // most the plan's dist_bound < 2^32-1.  The settle-limited search
+            // just did not find the shorter path.
+            if (outv && via < 0xFFFFFFFFull) outv->push_back({a.v, b.v, (uint32_t)via});
         }
         return count;
     }

@@ -271,7 +271,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
     auto witness = [&](uint32_t np, bool contract, uint32_t settle) {
         if (!np) return;
         ovf.ensure(np);
-        CH_HIP(hipMemsetAsync(ctr.p, 0, 8, st));  // ovf_n, err
+        CH_HIP(hipMemsetAsync(ctr.p, 0, 4, st));  // ovf_n
         const uint32_t* list = nullptr;
         uint32_t cnt = np;
         searches += np;
@@ -283,7 +283,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
             }
             chk::launch_witness(pairs.p, nullptr, np, overlay(), state.p, contract, settle, ws1.p,
                                 caps1, lanes1, tag1, lane_cap, slots.p,
-                                sflag.p, sc.p, ovf.p, ctr.p, ctr.p + 1, st);
+                                sflag.p, sc.p, ovf.p, ctr.p, st);
             tag1 += np + 1;
             read({ctr.p});
             cnt = hv.p[0];
@@ -301,7 +301,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
             CH_HIP(hipMemsetAsync(ctr.p + 4, 0, 4, st));
             chk::launch_witness_wave(pairs.p, list, cnt, overlay(), state.p, contract, settle,
                                      wave_blocks, size, slots.p, sflag.p, sc.p, out.p, ctr.p + 4,
-                                     ctr.p + 1, st);
+                                     st);
             wave_searches += cnt;
             read({ctr.p + 4});
             cnt = hv.p[0];
@@ -309,10 +309,9 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
             t_wave += now_seconds() - tw;
             tw = now_seconds();
         }
-        read({ctr.p + 1, ctr.p + 2});
-        const uint32_t err = hv.p[0], maxdeg = hv.p[1];
-        CPD_REQUIRE(!err, CPD_E_RANGE, "shortcut weight >= 2^32-1");
         if (!cnt) return;
+        read({ctr.p + 2});
+        const uint32_t maxdeg = hv.p[0];
         const uint32_t novf = cnt;
         big_searches += novf;
         // pushes <= 1 + settle x maxdeg, touched nodes <= that + targets
@@ -339,11 +338,10 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
         CH_HIP(hipMemsetAsync(ctr.p + 3, 0, 4, st));
         chk::launch_witness(pairs.p, list, novf, overlay(), state.p, contract, settle, ws2.p,
                             caps2, lanes2, tag2, 0xFFFFFFFFu, slots.p, sflag.p, sc.p, lost.p,
-                            ctr.p + 3, ctr.p + 1, st);
+                            ctr.p + 3, st);
         tag2 += novf + 1;
-        read({ctr.p + 3, ctr.p + 1});
+        read({ctr.p + 3});
         CPD_REQUIRE(!hv.p[0], CPD_E_HIP, "GPU contraction: witness workspace overflow");
-        CPD_REQUIRE(!hv.p[1], CPD_E_RANGE, "shortcut weight >= 2^32-1");
         t_big += now_seconds() - tw;
     };
     // priorities of list[0..k) (ch.cpp Contractor::priority / step 6)

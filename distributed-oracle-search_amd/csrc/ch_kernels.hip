@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void k_witness(
     const uint8_t* __restrict__ state, uint32_t contract, uint32_t settle, uint8_t* ws,
     WitnessCaps caps, uint64_t lane_bytes, uint32_t tag_base, uint32_t step_cap,
     uint4* __restrict__ slots, uint32_t* __restrict__ sflag, uint32_t* __restrict__ sc,
-    uint32_t* __restrict__ ovf, uint32_t* __restrict__ ovf_n, uint32_t* __restrict__ err) {
+    uint32_t* __restrict__ ovf, uint32_t* __restrict__ ovf_n) {
     const uint32_t lane = gid();
     const uint32_t stride = gridDim.x * blockDim.x;
     uint8_t* base = ws + lane_bytes * lane;
@@ -400,9 +400,10 @@ __global__ __launch_bounds__(256) void k_witness(
             }
             count += need;
             if (contract) {
-                if (need && via >= 0xFFFFFFFFull) atomicOr(err, 1u);
-                slots[pr.z + k] = need ? make_uint4(a.x, b.x, (uint32_t)via, 1u) : make_uint4(0, 0, 0, 0);
-                sflag[pr.z + k] = need;
+                // as ch.cpp: counted, but a weight >= 2^32-1 is never emitted
+                const bool emit = need && via < 0xFFFFFFFFull;
+                slots[pr.z + k] = emit ? make_uint4(a.x, b.x, (uint32_t)via, 1u) : make_uint4(0, 0, 0, 0);
+                sflag[pr.z + k] = emit;
             }
         }
         if (!contract && count) atomicAdd(&sc[v], count);
@@ -497,7 +498,7 @@ __global__ __launch_bounds__(64) void k_witness_wave(
     const uint4* __restrict__ pairs, const uint32_t* __restrict__ plist, uint32_t np, Overlay g,
     const uint8_t* __restrict__ state, uint32_t contract, uint32_t settle, uint4* __restrict__ slots,
     uint32_t* __restrict__ sflag, uint32_t* __restrict__ sc, uint32_t* __restrict__ ovf,
-    uint32_t* __restrict__ ovf_n, uint32_t* __restrict__ err) {
+    uint32_t* __restrict__ ovf_n) {
     extern __shared__ unsigned long long lds_raw[];
     using WL = WaveLds<kWH, kWP, kWT>;
     WL& S = *reinterpret_cast<WL*>(lds_raw);
@@ -698,9 +699,9 @@ __global__ __launch_bounds__(64) void k_witness_wave(
                     need = !(f && S.hdist[s] <= via);
                 }
                 if (contract) {
-                    if (need && via >= 0xFFFFFFFFull) atomicOr(err, 1u);
-                    slots[pr.z + k] = need ? make_uint4(a.x, b.x, (uint32_t)via, 1u) : make_uint4(0, 0, 0, 0);
-                    sflag[pr.z + k] = need;
+                    const bool emit = need && via < 0xFFFFFFFFull;
+                    slots[pr.z + k] = emit ? make_uint4(a.x, b.x, (uint32_t)via, 1u) : make_uint4(0, 0, 0, 0);
+                    sflag[pr.z + k] = emit;
                 }
             }
             count += __popcll(__ballot(need));
@@ -967,7 +968,7 @@ void launch_witness(const uint32_t* pairs, const uint32_t* plist, uint32_t np, O
                     const uint8_t* state, bool contract, uint32_t settle, void* ws,
                     WitnessCaps caps, uint32_t lanes, uint32_t tag_base, uint32_t step_cap,
                     uint32_t* slots, uint32_t* sflag, uint32_t* sc, uint32_t* ovf,
-                    uint32_t* ovf_n, uint32_t* err, hipStream_t s) {
+                    uint32_t* ovf_n, hipStream_t s) {
     if (!np) return;
     // lanes: a multiple of 64 (whole waves; 256-thread blocks when it allows)
     const uint32_t l = std::min<uint32_t>(lanes, ((np + 63u) / 64u) * 64u);
@@ -976,35 +977,35 @@ void launch_witness(const uint32_t* pairs, const uint32_t* plist, uint32_t np, O
                        reinterpret_cast<const uint4*>(pairs), plist, np, g, state,
                        contract ? 1u : 0u, settle, static_cast<uint8_t*>(ws), caps,
                        witness_lane_bytes(caps), tag_base, step_cap,
-                       reinterpret_cast<uint4*>(slots), sflag, sc, ovf, ovf_n, err);
+                       reinterpret_cast<uint4*>(slots), sflag, sc, ovf, ovf_n);
 }
 
 template <uint32_t H, uint32_t P, uint32_t T>
 void launch_ww(const uint32_t* pairs, const uint32_t* plist, uint32_t np, Overlay g,
                const uint8_t* state, bool contract, uint32_t settle, uint32_t blocks,
                uint32_t* slots, uint32_t* sflag, uint32_t* sc, uint32_t* ovf, uint32_t* ovf_n,
-               uint32_t* err, hipStream_t s) {
+               hipStream_t s) {
     auto k = k_witness_wave<H, P, T>;
     hipLaunchKernelGGL(k, dim3(std::min(np, blocks)), dim3(64), sizeof(WaveLds<H, P, T>), s,
                        reinterpret_cast<const uint4*>(pairs), plist, np, g, state,
                        contract ? 1u : 0u, settle, reinterpret_cast<uint4*>(slots), sflag, sc, ovf,
-                       ovf_n, err);
+                       ovf_n);
 }
 
 void launch_witness_wave(const uint32_t* pairs, const uint32_t* plist, uint32_t np, Overlay g,
                          const uint8_t* state, bool contract, uint32_t settle, uint32_t blocks,
                          int size, uint32_t* slots, uint32_t* sflag, uint32_t* sc, uint32_t* ovf,
-                         uint32_t* ovf_n, uint32_t* err, hipStream_t s) {
+                         uint32_t* ovf_n, hipStream_t s) {
     if (!np) return;
     if (size == 0)
         launch_ww<512, 384, 32>(pairs, plist, np, g, state, contract, settle, blocks, slots,
-                                sflag, sc, ovf, ovf_n, err, s);
+                                sflag, sc, ovf, ovf_n, s);
     else if (size == 1)
         launch_ww<1024, 768, 64>(pairs, plist, np, g, state, contract, settle, blocks, slots,
-                                 sflag, sc, ovf, ovf_n, err, s);
+                                 sflag, sc, ovf, ovf_n, s);
     else
         launch_ww<2048, 1792, 128>(pairs, plist, np, g, state, contract, settle, blocks, slots,
-                                   sflag, sc, ovf, ovf_n, err, s);
+                                   sflag, sc, ovf, ovf_n, s);
 }
 
 void launch_record(const uint32_t* S, uint32_t nS, uint32_t rank0, Overlay g, const uint32_t* upos,

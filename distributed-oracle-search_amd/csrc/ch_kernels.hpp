@@ -54,12 +54,13 @@ void launch_make_pairs(const uint32_t* list, uint32_t k, Overlay g, const uint32
 // with state 1, store (u, x, w, 1) or zeros per out-list slot in slots and
 // 1/0 in sflag; else atomicAdd the shortcut count to sc[node].  A search that
 // outgrows the lane workspace, or runs past step_cap pops + relaxations, is appended to ovf (count in ovf_n) and writes
-// nothing; a needed shortcut of weight >= 2^32-1 sets err.
+// nothing; a needed shortcut of weight >= 2^32-1 is counted but not stored
+// (ch.cpp shortcuts_via: it lies on no shortest path).
 void launch_witness(const uint32_t* pairs, const uint32_t* plist, uint32_t np, Overlay g,
                     const uint8_t* state, bool contract, uint32_t settle, void* ws,
                     WitnessCaps caps, uint32_t lanes, uint32_t tag_base, uint32_t step_cap,
                     uint32_t* slots, uint32_t* sflag, uint32_t* sc, uint32_t* ovf,
-                    uint32_t* ovf_n, uint32_t* err, hipStream_t s);
+                    uint32_t* ovf_n, hipStream_t s);
 // The same searches, one wave each with the search's table and heap in LDS
 // (size 0: 512 table / 384 heap
 // slots / 32 targets, 1: 1024 / 768 / 64, 2: 2048 / 1792 / 128): for the
@@ -67,7 +68,7 @@ void launch_witness(const uint32_t* pairs, const uint32_t* plist, uint32_t np, O
 void launch_witness_wave(const uint32_t* pairs, const uint32_t* plist, uint32_t np, Overlay g,
                          const uint8_t* state, bool contract, uint32_t settle, uint32_t blocks,
                          int size, uint32_t* slots, uint32_t* sflag, uint32_t* sc, uint32_t* ovf,
-                         uint32_t* ovf_n, uint32_t* err, hipStream_t s);
+                         uint32_t* ovf_n, hipStream_t s);
 // Record the contracted nodes S (ranks rank0 + i): rank[v], rec_* per rank,
 // their out-/in-lists copied to the up / down pools at upos / dpos (+ base),
 // neighbours' deleted / depth / aff updated, state[v] = 2.

@@ -137,8 +137,9 @@ int cpd_plan_create(const uint32_t* row_ptr, const uint32_t* dst, const uint32_t
         }
         side.join();
         // the graph's own errors first (as when they were checked before the
-        // hierarchy): a distance range the u32 path cannot hold also makes
-        // the contraction fail on a shortcut weight
+        // hierarchy).  The range check is the only one on weights: the
+        // contraction drops a candidate shortcut of weight >= 2^32-1 (under
+        // this bound it lies on no shortest path), it does not fail on it
         if (side_err) std::rethrow_exception(side_err);
         CPD_REQUIRE(p->dist_bound < 0xFFFFFFFFull, CPD_E_RANGE,
                     "graph distances may reach 2^32-1; the u32 distance path "

@@ -157,6 +157,82 @@ def wide_targets(name, g):
     return np.random.default_rng(1).permutation(g.n).astype(np.uint32)[:WIDE[name][3]]
 
 
+# Range and level-1 edge graphs (test_host_cpu.py pins what the GPU tests of
+# test_gpu_range_edges.py rely on).  Not in GRAPHS, for the reason above.
+
+def scaled_to_bound(g0, limit):
+    """g0 with every weight x floor(limit / dist_bound of g0): the plan's
+    distance bound lands just under `limit` (the factor is applied in u64)."""
+    bound1 = cpd.Plan(g0, hierarchy=False).info()["dist_bound"]
+    scale = int(limit) // int(bound1)
+    w = g0.w.astype(np.uint64) * np.uint64(scale)
+    assert scale >= 1 and int(w.max()) <= 0xFFFFFFFF
+    return cpd.RoadGraph(g0.row_ptr, g0.dst, w.astype(np.uint32), g0.x, g0.y)
+
+
+TOP_LIMIT = 0xFFFFFFFD  # the largest bound at which narrow rows stay on
+
+# strongly connected graphs whose distance bound is just under TOP_LIMIT
+TOP = {
+    "synth": lambda: scaled_to_bound(cpd.synth_road_graph(40, 40, seed=12), TOP_LIMIT),
+    "deg8": lambda: scaled_to_bound(deg8_graph(), TOP_LIMIT),
+    # ... and edges whose w + d(head) wraps past 2^32 (deg8_heavy_graph)
+    "deg8heavy": lambda: scaled_to_bound(deg8_heavy_graph(), TOP_LIMIT),
+}
+
+
+def deg8_heavy_graph():
+    """deg8_graph's construction, the last chord of every node made heavy: its
+    weight is the distance bound of the graph without these chords, less 1.
+    No shortest path takes one, so distances and bound stay what they were —
+    but w + d(head) passes the bound for most (heavy edge, target) pairs:
+    scaled to the top of the range, those adds wrap past 2^32 (on the scaled
+    deg8_graph and synth graph no edge's add can: the largest w + d(head)
+    over all targets is 0xD2D2D2C4 and 0xA15A8628)."""
+    rng = np.random.default_rng(8)
+    n = 400
+    light, heavy = [], []
+    for a in range(n):
+        light.append((a, (a + 1) % n, int(rng.integers(1, 4))))
+        k = int(rng.integers(4, 8))
+        for i in range(k):
+            e = (a, int(rng.integers(0, n)), int(rng.integers(1, 4)))
+            (heavy if i == k - 1 else light).append(e)
+    bound = cpd.Plan(graph_from_edges(n, light), hierarchy=False).info()["dist_bound"]
+    return graph_from_edges(n, light + [(a, b, bound - 1) for a, b, _ in heavy])
+
+
+def two_cycle(a):
+    """0 -> 1 of weight a, 1 -> 0 of weight 1: the distance bound is a."""
+    return graph_from_edges(2, [(0, 1, a), (1, 0, 1)])
+
+
+def stars(nh, seed):
+    """A one-way ring of nh hubs (nodes 0..nh-1, weights 1..8), each hub with
+    0..6 pendant nodes joined to it both ways (weights 1..8).  Ring edges
+    first, then the pendants in hub order.  The pendants are contracted first
+    (level 0), so a hub with many of them is a level-1 node whose leaf arcs
+    are its out-arcs to them — up to 6, and a 7th when the next hub of the
+    ring is a leaf of the hierarchy too."""
+    rng = np.random.default_rng(seed)
+    edges = [(h, (h + 1) % nh, int(rng.integers(1, 9))) for h in range(nh)]
+    n = nh
+    for h in range(nh):
+        for _ in range(int(rng.integers(0, 7))):
+            edges.append((h, n, int(rng.integers(1, 9))))
+            edges.append((n, h, int(rng.integers(1, 9))))
+            n += 1
+    return graph_from_edges(n, edges)
+
+
+def wide_level1(ch):
+    """Nodes of an exported hierarchy at sweep level 1 with more than 4
+    down-arcs, and each one's down-arc count."""
+    cnt = np.diff(ch["dn_off"].astype(np.int64))
+    v = np.nonzero((ch["level_up"] == 1) & (cnt > 4))[0]
+    return v, cnt[v]
+
+
 GRAPHS = {
     "synth": lambda: cpd.synth_road_graph(40, 30, seed=7),
     "ties": tie_graph,

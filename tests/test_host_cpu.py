@@ -13,7 +13,7 @@ from scipy.sparse.csgraph import connected_components
 
 import cpd
 import oracle
-from graphs import GRAPHS
+from graphs import GRAPHS, TOP, TOP_LIMIT, stars, two_cycle, wide_level1
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -91,10 +91,9 @@ def _phast(ch, n, t):
     return d.astype(np.uint32)
 
 
-@pytest.mark.parametrize("name", sorted(GRAPHS))
-def test_hierarchy_sweeps_give_exact_distances(name):
-    g = GRAPHS[name]()
-    plan = cpd.Plan(g, threads=2)
+def _check_hierarchy_sweeps(g, plan, name):
+    """The exported hierarchy is well formed and its two sweeps (_phast) give
+    the oracle's distances to six seeded targets."""
     ch = plan.export_ch()
     rank = ch["rank"]
     assert np.array_equal(np.sort(rank), np.arange(g.n))
@@ -109,6 +108,57 @@ def test_hierarchy_sweeps_give_exact_distances(name):
     for t in rng.choice(g.n, size=min(g.n, 6), replace=False):
         ref = oracle.reverse_dijkstra(g.row_ptr, g.dst, g.w, t)
         np.testing.assert_array_equal(_phast(ch, g.n, t), ref, err_msg=f"{name} t={t}")
+
+
+@pytest.mark.parametrize("name", sorted(GRAPHS))
+def test_hierarchy_sweeps_give_exact_distances(name):
+    g = GRAPHS[name]()
+    _check_hierarchy_sweeps(g, cpd.Plan(g, threads=2), name)
+
+
+@pytest.mark.parametrize("name,settle", [("synth", 0), ("synth", 3), ("deg8", 0), ("deg8", 3),
+                                         ("deg8heavy", 0)])
+def test_top_of_range_plans_are_accepted_and_exact(name, settle):
+    """Distances just under 2^32-1: the plan is accepted (a candidate shortcut
+    the settle-limited witness search could not rule out may weigh 2^32-1 or
+    more; it lies on no shortest path and is dropped, not an error) and its
+    sweeps are exact.  settle=3 makes nearly every candidate a shortcut."""
+    g = TOP[name]()
+    plan = cpd.Plan(g, settle=settle)
+    bound = plan.info()["dist_bound"]
+    assert bound <= TOP_LIMIT
+    _check_hierarchy_sweeps(g, plan, f"{name} settle={settle}")
+    # the graph really reaches the top: the bound is the sum of two
+    # eccentricities, each a real distance
+    far = 0
+    for t in range(g.n):
+        d = oracle.reverse_dijkstra(g.row_ptr, g.dst, g.w, t)
+        far = max(far, int(d[d != oracle.INF].max()))
+    assert far >= bound // 2, (far, bound)
+
+
+def test_plan_range_limit_itself():
+    """dist_bound < 2^32-1 is the promise: 0xFFFFFFFE is accepted (no
+    hierarchy arc is lost to the limit), 0xFFFFFFFF refused."""
+    g = two_cycle(0xFFFFFFFE)
+    plan = cpd.Plan(g)
+    assert plan.info()["dist_bound"] == 0xFFFFFFFE
+    ch = plan.export_ch()
+    assert sorted(ch["up_w"].tolist() + ch["dn_w"].tolist()) == [1, 0xFFFFFFFE]
+    with pytest.raises(cpd.CpdError) as e:
+        cpd.Plan(two_cycle(0xFFFFFFFF))
+    assert e.value.code == cpd.CPD_E_RANGE
+
+
+def test_stars_generator_keeps_its_shape():
+    """What test_gpu_range_edges.py relies on: 8-bit first-move sets and
+    level-1 nodes whose closed form reads leaf arcs past the four the
+    down-sweep descriptor holds."""
+    g = stars(300, 3)
+    assert 5 <= int(np.diff(g.row_ptr.astype(np.int64)).max()) <= 8
+    v, cnt = wide_level1(cpd.Plan(g).export_ch())
+    assert len(v) >= 10
+    assert np.any(cnt == 5) and np.any(cnt >= 7)
 
 
 def test_hierarchy_is_deterministic_across_threads():
