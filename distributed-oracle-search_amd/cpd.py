@@ -54,6 +54,7 @@ EXPORTED = [
     "cpd_device_mem_info", "cpd_rows_move_words", "cpd_rows_export_moves",
     "cpd_index_append_moves", "cpd_device_arena", "cpd_device_arena_release", "cpd_batch_bytes",
     "cpd_rows_move_bits", "cpd_graph_move_bits", "cpd_bucket_bytes", "cpd_space_check",
+    "cpd_query_paths", "cpd_query_paths_fetch",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
@@ -537,6 +538,7 @@ class Index:
     def __init__(self, graph: Graph, rows: Rows | None = None, row_targets=None,
                  offsets=None, runs=None, _handle=None):
         self.graph = graph
+        self._nq, self._path_offsets = 0, None  # prepared queries; offsets of their paths
         self._h = C.c_void_p()
         if _handle is not None:
             self._h = _handle
@@ -604,6 +606,7 @@ class Index:
     def query(self, s, t, k_moves: int = -1):
         s, t = _u32(s), _u32(t)
         nq = len(s)
+        self._nq, self._path_offsets = 0, None  # cpd_query_batch prepares and runs
         cost = np.empty(nq, np.uint64)
         hops = np.empty(nq, np.uint32)
         fin = np.empty(nq, np.uint8)
@@ -611,16 +614,63 @@ class Index:
         _check(lib.cpd_query_batch(self._h, _ptr(s, u32p), _ptr(t, u32p), C.c_uint32(nq),
                                    C.c_int32(k_moves), _ptr(cost, u64p), _ptr(hops, u32p),
                                    _ptr(fin, u8p), C.byref(st)))
+        self._nq = nq
         return cost, hops, fin, {k: getattr(st, k) for k, _ in QueryStats._fields_}
 
     def prepare(self, s, t) -> None:
         s, t = _u32(s), _u32(t)
+        self._nq, self._path_offsets = 0, None  # the library drops the last batch's paths
         _check(lib.cpd_query_prepare(self._h, _ptr(s, u32p), _ptr(t, u32p), C.c_uint32(len(s))))
+        self._nq = len(s)
 
     def run(self, k_moves: int = -1) -> dict:
+        self._path_offsets = None
         st = QueryStats()
         _check(lib.cpd_query_run(self._h, C.c_int32(k_moves), C.byref(st)))
         return {k: getattr(st, k) for k, _ in QueryStats._fields_}
+
+    def paths(self, s, t, k_moves: int = -1):
+        """The table-search walks of (s, t) with their nodes (cpd_query_paths):
+        (offsets u64[nq + 1], nodes u32[offsets[-1]], cost, hops, finished,
+        stats); path q is nodes[offsets[q]:offsets[q + 1]], hops[q] + 1 node
+        ids from s[q] to where the walk ended."""
+        self.prepare(s, t)
+        nq = len(s)
+        offsets, st = self.paths_run(k_moves)
+        nodes = self.paths_fetch(0, nq)
+        cost = np.empty(nq, np.uint64)
+        hops = np.empty(nq, np.uint32)
+        fin = np.empty(nq, np.uint8)
+        _check(lib.cpd_query_fetch(self._h, _ptr(cost, u64p), _ptr(hops, u32p), _ptr(fin, u8p)))
+        return offsets, nodes, cost, hops, fin, st
+
+    def paths_run(self, k_moves: int = -1):
+        """cpd_query_paths on the prepared queries: (offsets u64[nq + 1], stats).
+        The offsets are kept: paths_fetch sizes its buffers from them."""
+        self._path_offsets = None
+        offsets = np.empty(self._nq + 1, np.uint64)
+        st = QueryStats()
+        _check(lib.cpd_query_paths(self._h, C.c_int32(k_moves), _ptr(offsets, u64p), C.byref(st)))
+        self._path_offsets = offsets.copy()
+        return offsets, {k: getattr(st, k) for k, _ in QueryStats._fields_}
+
+    def paths_fetch(self, first: int, count: int) -> np.ndarray:
+        """Nodes of paths [first, first + count) of the last paths() /
+        paths_run(), back to back (cpd_query_paths_fetch).  The library copies
+        as many nodes as ITS offsets say, so this refuses (CPD_E_ARG, as the
+        library would) whenever the offsets of that very call are not at hand
+        or the range leaves them: the buffer is never sized by guesswork."""
+        off = self._path_offsets
+        if off is None:
+            raise CpdError(CPD_E_ARG, "paths fetch: no paths() / paths_run() on the prepared "
+                                      "queries yet")
+        if first < 0 or count < 0 or first + count > len(off) - 1:
+            raise CpdError(CPD_E_ARG, f"paths fetch: queries [{first}, {first + count}) past the "
+                                      f"batch's {len(off) - 1}")
+        nodes = np.empty(int(off[first + count]) - int(off[first]), np.uint32)
+        _check(lib.cpd_query_paths_fetch(self._h, C.c_uint32(first), C.c_uint32(count),
+                                         _ptr(nodes, u32p)))
+        return nodes
 
     def search(self, s, t, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
                capacity=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,

@@ -197,6 +197,7 @@ struct cpd_graph {
     std::vector<uint32_t> order;       // node -> column
     std::vector<uint32_t> inv;         // column -> node
     DevBuf<uint32_t> order_d;          // node -> column (query preparation)
+    DevBuf<uint32_t> inv_d;            // column -> node (path extraction; at first use)
     std::vector<uint32_t> edge_perm;   // column-space edge -> file edge
     std::vector<uint32_t> w_free_col;  // free-flow weights, column-space edges
     std::vector<uint32_t> rowc_host;   // column-space row_ptr (host copy)
@@ -751,6 +752,13 @@ struct cpd_index {
     DevBuf<uint64_t> cost;
     DevBuf<uint8_t> fin;
     DevBuf<unsigned long long> agg;
+    // path extraction (cpd_query_paths): node counts and path offsets in the
+    // caller's order (device, host copy), the nodes; paths_ready: they are
+    // those of the prepared queries
+    DevBuf<uint64_t> plens, poff;
+    std::vector<uint64_t> poff_h;
+    DevBuf<uint32_t> pnodes;
+    bool paths_ready = false;
 };
 
 void cpd_rows::settle() const {
@@ -2511,6 +2519,7 @@ int cpd_query_prepare(cpd_index* ix, const uint32_t* s, const uint32_t* t, uint3
         // columns; the caller's order comes back in cpd_query_fetch
         ix->nq = 0;
         ix->searched = false;
+        ix->paths_ready = false;
         const size_t m = std::max<uint32_t>(nq, 1u);
         for (DevBuf<uint32_t>* b : {&ix->qin_s, &ix->qin_t, &ix->qkey, &ix->qkey2, &ix->qval,
                                     &ix->qperm, &ix->qs, &ix->qt, &ix->qrow, &ix->hops})
@@ -2571,6 +2580,73 @@ void ensure_dense(cpd_index* ix) {
     ix->dense_ready = true;
 }
 
+// The table-search walk of the prepared queries (cpd_query_run; the count
+// pass of cpd_query_paths): cost / hops / fin in sorted order, sums in agg.
+// Returns the launch's algorithmic bytes when timing is on (else 0).
+double run_walk(cpd_index* ix, int32_t k_moves, cpd_query_stats* st) {
+    cpd_graph* g = ix->g;
+    g->select();
+    const uint32_t nq = ix->nq;
+    const bool dense = ix->use_dense();
+    if (dense && !ix->dense_ready) ensure_dense(ix);
+    HIP_CHECK(hipMemsetAsync(ix->agg.p, 0, 4 * sizeof(unsigned long long), g->stream));
+    hipEvent_t a = g->get_event(), b = g->get_event();
+    HIP_CHECK(hipEventRecord(a, g->stream));
+    const uint32_t* adj = ix->custom_w ? ix->adj_sel.p : g->adj.p;
+    (void)hipGetLastError();
+    if (nq && dense)
+        launch_table_search_dense(adj, g->adj_shift, ix->dense.p, g->npad, g->tlb, ix->qs.p,
+                                  ix->qt.p, ix->qrow.p, nq, k_moves, g->n, ix->cost.p,
+                                  ix->hops.p, ix->fin.p, ix->agg.p, g->stream);
+    else if (nq)
+        launch_table_search(adj, g->adj_shift, ix->off.p, ix->runs.p, ix->qs.p, ix->qt.p,
+                            ix->qrow.p, nq, k_moves, g->n, ix->cost.p, ix->hops.p,
+                            ix->fin.p, ix->agg.p, g->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(b, g->stream));
+    unsigned long long hagg[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(hagg, ix->agg.p, sizeof hagg, hipMemcpyDeviceToHost, g->stream));
+    HIP_CHECK(hipStreamSynchronize(g->stream));
+    if (hagg[3] && switches().search_trace)
+        std::fprintf(stderr, "[walk] %llu queries, %llu moves, %llu of them taken from "
+                     "earlier walks' suffixes\n", (unsigned long long)nq, hagg[1], hagg[3]);
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    g->ev_pool.push_back(a);
+    g->ev_pool.push_back(b);
+    double bytes = 0.0;
+    if (g->timing) {
+        Agg& ag = g->agg[dense ? "table_search_dense" : "table_search"];
+        ag.launches++;
+        ag.ms += ms;
+        if (dense) {
+            // per query 8 (s,t) + 13 (outputs) + 4 (row); per move one
+            // 4-B move word + one 8-B packed edge
+            bytes = 25.0 * nq + 12.0 * (double)hagg[1];
+        } else {
+            // SURVEY.md §8(d) B_q = 8 + 12 + 8 + L * (4 ceil(log2 R) + 16)
+            double mean_log = 0.0;
+            if (ix->nrows) {
+                double s = 0.0;
+                for (uint32_t i = 0; i < ix->nrows; ++i)
+                    s += std::ceil(std::log2((double)std::max<uint64_t>(
+                        2, ix->offsets[i + 1] - ix->offsets[i])));
+                mean_log = s / ix->nrows;
+            }
+            bytes = 28.0 * nq + (double)hagg[1] * (4.0 * mean_log + 16.0);
+        }
+        ag.bytes += bytes;
+    }
+    if (st) {
+        st->queries = nq;
+        st->finished = hagg[0];
+        st->hops = hagg[1];
+        st->cost = hagg[2];
+        st->kernel_ms = ms;
+    }
+    return bytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2596,64 +2672,124 @@ int cpd_index_get_mode(const cpd_index* ix, int* mode) {
 int cpd_query_run(cpd_index* ix, int32_t k_moves, cpd_query_stats* st) {
     return guarded([&] {
         CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        ix->paths_ready = false;
+        run_walk(ix, k_moves, st);
+    });
+}
+
+int cpd_query_paths(cpd_index* ix, int32_t k_moves, uint64_t* offsets, cpd_query_stats* st) {
+    return guarded([&] {
+        CPD_REQUIRE(ix && offsets, CPD_E_ARG, "paths: null argument");
         cpd_graph* g = ix->g;
         g->select();
+        hipStream_t s = g->stream;
         const uint32_t nq = ix->nq;
-        const bool dense = ix->use_dense();
-        if (dense && !ix->dense_ready) ensure_dense(ix);
-        HIP_CHECK(hipMemsetAsync(ix->agg.p, 0, 4 * sizeof(unsigned long long), g->stream));
-        hipEvent_t a = g->get_event(), b = g->get_event();
-        HIP_CHECK(hipEventRecord(a, g->stream));
-        const uint32_t* adj = ix->custom_w ? ix->adj_sel.p : g->adj.p;
-        (void)hipGetLastError();
-        if (nq && dense)
-            launch_table_search_dense(adj, g->adj_shift, ix->dense.p, g->npad, g->tlb, ix->qs.p,
-                                      ix->qt.p, ix->qrow.p, nq, k_moves, g->n, ix->cost.p,
-                                      ix->hops.p, ix->fin.p, ix->agg.p, g->stream);
-        else if (nq)
-            launch_table_search(adj, g->adj_shift, ix->off.p, ix->runs.p, ix->qs.p, ix->qt.p,
-                                ix->qrow.p, nq, k_moves, g->n, ix->cost.p, ix->hops.p,
-                                ix->fin.p, ix->agg.p, g->stream);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(b, g->stream));
-        unsigned long long hagg[4] = {0, 0, 0, 0};
-        HIP_CHECK(hipMemcpyAsync(hagg, ix->agg.p, sizeof hagg, hipMemcpyDeviceToHost, g->stream));
-        HIP_CHECK(hipStreamSynchronize(g->stream));
-        if (hagg[3] && switches().search_trace)
-            std::fprintf(stderr, "[walk] %llu queries, %llu moves, %llu of them taken from "
-                         "earlier walks' suffixes\n", (unsigned long long)nq, hagg[1], hagg[3]);
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        g->ev_pool.push_back(a);
-        g->ev_pool.push_back(b);
-        if (g->timing) {
-            Agg& ag = g->agg[dense ? "table_search_dense" : "table_search"];
-            ag.launches++;
-            ag.ms += ms;
-            if (dense) {
-                // per query 8 (s,t) + 13 (outputs) + 4 (row); per move one
-                // 4-B move word + one 8-B packed edge
-                ag.bytes += 25.0 * nq + 12.0 * (double)hagg[1];
-            } else {
-                // SURVEY.md §8(d) B_q = 8 + 12 + 8 + L * (4 ceil(log2 R) + 16)
-                double mean_log = 0.0;
-                if (ix->nrows) {
-                    double s = 0.0;
-                    for (uint32_t i = 0; i < ix->nrows; ++i)
-                        s += std::ceil(std::log2((double)std::max<uint64_t>(
-                            2, ix->offsets[i + 1] - ix->offsets[i])));
-                    mean_log = s / ix->nrows;
-                }
-                ag.bytes += 28.0 * nq + (double)hagg[1] * (4.0 * mean_log + 16.0);
+        CPD_REQUIRE(nq < 0x7FFFFFFFu, CPD_E_RANGE, "paths: too many queries for one batch");
+        ix->paths_ready = false;
+        // count: the walk itself (hops, cost, fin in sorted order; agg)
+        const double walk_bytes = run_walk(ix, k_moves, st);
+        if (!nq) {
+            offsets[0] = 0;
+            ix->poff_h.assign(1, 0);
+            ix->paths_ready = true;
+            return;
+        }
+        // offsets: hops to the caller's order, + 1, exclusive sum
+        if (!g->inv_d.p) g->inv_d.upload(g->inv.data(), g->n, s);
+        ix->qout.alloc((size_t)nq * 8u);
+        ix->plens.alloc((size_t)nq + 1u);
+        ix->poff.alloc((size_t)nq + 1u);
+        size_t scan_bytes = 0;
+        HIP_CHECK(path_scan_bytes(nq, &scan_bytes));
+        ix->qsort_tmp.alloc(scan_bytes);
+        // the steps' events go back to the pool however this call ends
+        struct Events {
+            cpd_graph* g;
+            hipEvent_t e[3];
+            explicit Events(cpd_graph* gr) : g(gr), e{gr->get_event(), gr->get_event(), gr->get_event()} {}
+            ~Events() {
+                for (hipEvent_t x : e) g->ev_pool.push_back(x);
             }
+        } ev(g);
+        const hipEvent_t e0 = ev.e[0], e1 = ev.e[1], e2 = ev.e[2];
+        HIP_CHECK(hipEventRecord(e0, s));
+        uint32_t* hops_c = reinterpret_cast<uint32_t*>(ix->qout.p);
+        launch_scatter_u32(ix->hops.p, ix->qperm.p, nq, 1u, hops_c, s);
+        HIP_CHECK(launch_path_offsets(ix->qsort_tmp.p, ix->qsort_tmp.n, hops_c, nq, ix->plens.p,
+                                      ix->poff.p, s));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(e1, s));
+        ix->poff_h.resize((size_t)nq + 1u);
+        HIP_CHECK(hipMemcpyAsync(ix->poff_h.data(), ix->poff.p, ((size_t)nq + 1u) * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        const uint64_t total = ix->poff_h[nq];
+        // fill: the same walks once more, storing their nodes
+        // (from the arena when there is one: it is a bump allocator, so a
+        // batch with more nodes than any before it carves a new buffer and
+        // the old one's bytes stay taken until cpd_device_arena_release; a
+        // batch that fits the buffer it has allocates nothing)
+        try {
+            ArenaScope carve;
+            ix->pnodes.alloc((size_t)total);
+        } catch (const Error& e) {
+            (void)hipGetLastError();
+            if (e.code != CPD_E_OOM) throw;
+            throw Error(CPD_E_OOM, "paths: " + std::to_string(4ull * total) + " bytes of HBM for " +
+                                       std::to_string(total) + " path nodes of " +
+                                       std::to_string(nq) + " queries do not fit");
         }
-        if (st) {
-            st->queries = nq;
-            st->finished = hagg[0];
-            st->hops = hagg[1];
-            st->cost = hagg[2];
-            st->kernel_ms = ms;
+        const bool dense = ix->use_dense();
+        const uint32_t* adj = ix->custom_w ? ix->adj_sel.p : g->adj.p;
+        if (dense)
+            launch_table_paths_dense(adj, g->adj_shift, ix->dense.p, g->npad, g->tlb, ix->qs.p,
+                                     ix->qt.p, ix->qrow.p, ix->qperm.p, ix->poff.p, g->inv_d.p, nq,
+                                     k_moves, g->n, ix->pnodes.p, s);
+        else
+            launch_table_paths(adj, g->adj_shift, ix->off.p, ix->runs.p, ix->qs.p, ix->qt.p,
+                               ix->qrow.p, ix->qperm.p, ix->poff.p, g->inv_d.p, nq, k_moves, g->n,
+                               ix->pnodes.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(e2, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        float ms_off = 0.f, ms_fill = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms_off, e0, e1));
+        HIP_CHECK(hipEventElapsedTime(&ms_fill, e1, e2));
+        if (g->timing) {
+            // offsets: hops read twice and written once (4 B), lens and poff
+            // written and read (8 B each way)
+            Agg& ao = g->agg["table_paths_offsets"];
+            ao.launches++;
+            ao.ms += ms_off;
+            ao.bytes += 44.0 * nq;
+            // fill: the walk's bytes + the stored nodes + the cursors
+            Agg& af = g->agg[dense ? "table_paths_dense" : "table_paths"];
+            af.launches++;
+            af.ms += ms_fill;
+            af.bytes += walk_bytes + 4.0 * (double)total + 8.0 * nq;
         }
+        std::memcpy(offsets, ix->poff_h.data(), ((size_t)nq + 1u) * sizeof(uint64_t));
+        ix->paths_ready = true;
+    });
+}
+
+int cpd_query_paths_fetch(cpd_index* ix, uint32_t first, uint32_t count, uint32_t* nodes) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        CPD_REQUIRE(ix->paths_ready, CPD_E_ARG,
+                    "paths fetch: no cpd_query_paths on the prepared queries yet");
+        CPD_REQUIRE((uint64_t)first + count <= ix->nq, CPD_E_ARG,
+                    "paths fetch: queries [" + std::to_string(first) + ", " +
+                        std::to_string((uint64_t)first + count) + ") past the batch's " +
+                        std::to_string(ix->nq));
+        const uint64_t a = ix->poff_h[first], b = ix->poff_h[(size_t)first + count];
+        if (a == b) return;
+        CPD_REQUIRE(nodes, CPD_E_ARG, "paths fetch: null argument");
+        cpd_graph* g = ix->g;
+        g->select();
+        HIP_CHECK(hipMemcpyAsync(nodes, ix->pnodes.p + a, (size_t)(b - a) * sizeof(uint32_t),
+                                 hipMemcpyDeviceToHost, g->stream));
+        HIP_CHECK(hipStreamSynchronize(g->stream));
     });
 }
 

@@ -2618,6 +2618,15 @@ __global__ __launch_bounds__(256) void scatter_rows(const T* __restrict__ in,
     out[(size_t)perm[q] * k + j] = in[i];
 }
 
+// path extraction: node counts of the walks, hops + 1, widened for the 64-bit
+// exclusive sum (nq + 1 values; the last one only closes the sum)
+__global__ __launch_bounds__(256) void path_lens(const uint32_t* __restrict__ hops, uint32_t nq,
+                                                 uint64_t* __restrict__ lens) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nq) return;
+    lens[i] = i < nq ? (uint64_t)hops[i] + 1u : 0u;
+}
+
 // Table-search extraction (table_walk below).  cur/t are columns; the run for
 // column cur is found by galloping from the previous hop's run (consecutive
 // path nodes have nearby DFS columns), then binary search inside the bracket:
@@ -3026,6 +3035,113 @@ __global__ __launch_bounds__(256) void table_walk(
         walk_hops<SHIFT, ILP>(w, adj, rows);  // one hop of every walking slot
     }
     wave_stats(sum_cost, sum_hops, sum_fin, agg);
+}
+
+// Path extraction (cpd_query_paths): table_walk's walk once more, keeping its
+// nodes.  A count pass (table_walk itself) gave every query's hops; poff is
+// the exclusive sum of hops + 1 in the CALLER's order, so path q is
+// nodes[poff[q] .. poff[q + 1]).  The wave-owns-a-chunk / lane-refill frame,
+// the retire condition and the hop (walk_begin / walk_hops) are table_walk's,
+// so every column's move is the one the count pass took and a lane ends with
+// hops == poff[q + 1] - poff[q] - 1.
+// The walk works in columns, the output is node ids (node_of_col).  The node a
+// lane stands on is gathered BEFORE the hop's loads are issued and stored
+// after the hop advanced (at index hops-before-the-hop), so the gather's
+// latency hides behind the hop's own loads instead of following them; the
+// node a walk ends on (t, or where it stopped) is stored when the lane
+// retires.  Every node is stored exactly once, in path order, inside the
+// lane's path (`room` keeps it there should the two passes ever disagree).
+// Store shape: a 4-B store per hop per lane made one L2 -> fabric write
+// request per node (DESIGN.md §3 "Path extraction"), so the nodes of every
+// 64-B line that lies wholly inside the lane's path are staged in LDS —
+// kPathStage nodes per lane, 4 KiB per wave; slot s of a lane at dword
+// ((s >> 2) * 64 + lane) * 4 + (s & 3), a lane's quad contiguous and the
+// wave's quads side by side — and the line is written with four 16-B stores
+// once its last slot is filled.  The count pass gave the path's length, so a
+// lane knows its whole lines when it begins: the nodes before the first and
+// after the last of them (the unaligned head and tail, < 16 each) are stored
+// 4 B at a time, and nothing is left to flush when the lane retires.
+constexpr uint32_t kPathStage = 16;
+
+template <int SHIFT, class Rows>
+__global__ __launch_bounds__(256) void table_walk_paths(
+    const uint2* __restrict__ adj, Rows rows, const uint32_t* __restrict__ qs,
+    const uint32_t* __restrict__ qt, const uint32_t* __restrict__ qrow,
+    const uint32_t* __restrict__ qperm, const uint64_t* __restrict__ poff,
+    const uint32_t* __restrict__ node_of_col, uint32_t nq, uint32_t chunk, uint32_t limit,
+    uint32_t* __restrict__ nodes) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t q0l = wave * chunk;
+    const uint32_t q0 = q0l < nq ? (uint32_t)q0l : nq;
+    const uint32_t q1 = (uint32_t)min((uint64_t)nq, q0l + chunk);
+    extern __shared__ uint32_t path_stage[];  // kPathStage * 64 per wave
+    uint32_t* mine = path_stage + (threadIdx.x >> 6) * (kPathStage * 64u) + lane * 4u;
+    WalkState w[1];
+    uint32_t* out = nodes;  // this lane's path
+    uint32_t room = 0;      // its node count
+    uint32_t lo = 0;        // ... before its first whole 64-B line
+    uint32_t nfull = 0;     // ... in whole lines
+    uint32_t next = q0;     // wave-uniform: first query of the chunk not yet started
+    w[0].q = kIdleQ;        // idle: column 0 of row 0 stays loadable
+    w[0].cur = 0;
+    w[0].t = 0;
+    w[0].hops = 0;
+    w[0].bad = false;
+    w[0].cost = 0;
+    w[0].pos = 0;
+    w[0].R = 0;
+    w[0].row = rows_base(rows);
+    auto begin = [&](uint32_t q) {
+        walk_begin(w[0], q, qs, qt, qrow, rows);
+        const uint32_t c = qperm[q];
+        const uint64_t o = poff[c];
+        out = nodes + o;
+        room = (uint32_t)(poff[c + 1] - o);
+        lo = (kPathStage - (uint32_t)(o & (kPathStage - 1u))) & (kPathStage - 1u);
+        nfull = room > lo ? (room - lo) & ~(kPathStage - 1u) : 0u;
+    };
+    auto put = [&](uint32_t idx, uint32_t v) {  // node idx of the lane's path
+        const uint32_t r = idx - lo;
+        if (r < nfull) {
+            const uint32_t slot = r & (kPathStage - 1u);
+            mine[(slot >> 2) * 256u + (slot & 3u)] = v;
+            if (slot == kPathStage - 1u) {  // the line is whole: 64 B, aligned
+                uint4* line = reinterpret_cast<uint4*>(out + (idx - (kPathStage - 1u)));
+#pragma unroll
+                for (uint32_t k = 0; k < kPathStage / 4u; ++k) {
+                    const uint32_t* m4 =
+                        static_cast<const uint32_t*>(__builtin_assume_aligned(mine + k * 256u, 16));
+                    line[k] = make_uint4(m4[0], m4[1], m4[2], m4[3]);
+                }
+            }
+        } else if (idx < room) {
+            out[idx] = v;
+        }
+    };
+    if (next + lane < q1) begin(next + lane);
+    next = min(q1, next + 64u);
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    for (;;) {
+        const bool idle = w[0].q == kIdleQ;
+        const bool done = !idle && (w[0].cur == w[0].t || w[0].hops >= limit || w[0].bad);
+        const uint64_t m = __ballot(done);
+        if (m) {
+            if (done) {
+                put(w[0].hops, node_of_col[w[0].cur]);
+                const uint32_t nqi = next + (uint32_t)__builtin_popcountll(m & lt_mask);
+                if (nqi < q1) begin(nqi);
+                else w[0].q = kIdleQ;
+            }
+            next = min(q1, next + (uint32_t)__builtin_popcountll(m));
+        }
+        const bool live = w[0].q != kIdleQ;
+        if (!__any(live)) break;
+        const uint32_t h0 = w[0].hops;
+        const uint32_t v = node_of_col[w[0].cur];  // in flight beside the hop's loads
+        walk_hops<SHIFT, 1>(w, adj, rows);
+        if (live && w[0].hops != h0) put(h0, v);
+    }
 }
 
 __device__ void wave_stats(uint64_t cost, uint32_t hops, uint32_t fin,
@@ -4421,6 +4537,72 @@ void launch_table_search(const uint32_t* adj, uint32_t shift, const uint64_t* of
     launch_walk(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs}, qs, qt,
                 qrow, nq, walk_limit(kmoves, n), cost, hops, fin, agg, kRleWaves, 1u << 30, s,
                 kRleWpb);
+}
+
+// Path extraction's fill pass: launch_walk's chunking with the walk's own
+// constants (kDenseWaves / kDenseWpb, kRleWaves / kRleWpb).
+template <class Rows>
+static void launch_walk_paths(const uint2* adj, uint32_t shift, const Rows& rows,
+                              const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
+                              const uint32_t* qperm, const uint64_t* poff,
+                              const uint32_t* node_of_col, uint32_t nq, uint32_t limit,
+                              uint32_t* nodes, uint32_t waves_target, uint32_t chunk_max,
+                              hipStream_t s, uint32_t wpb) {
+    constexpr uint32_t unit = 64u;
+    uint64_t chunk = ((uint64_t)nq + waves_target - 1u) / waves_target;
+    chunk = std::min<uint64_t>(chunk, std::max(unit, chunk_max));
+    chunk = std::max<uint64_t>(unit, (chunk + unit - 1u) / unit * unit);
+    const uint64_t waves = ((uint64_t)nq + chunk - 1u) / chunk;
+    const dim3 grid((uint32_t)std::max<uint64_t>(1u, (waves + wpb - 1u) / wpb)), blk(64u * wpb);
+    const uint32_t c = (uint32_t)chunk;
+    const size_t shm = (size_t)wpb * kern::kPathStage * 64u * sizeof(uint32_t);
+#define CPD_WALK_PATHS(SH)                                                                    \
+    launch_shm(kern::table_walk_paths<SH, Rows>, grid, blk, shm, s, adj, rows, qs, qt, qrow, qperm, \
+               poff, node_of_col, nq, c, limit, nodes)
+    switch (shift) {
+        case 0: CPD_WALK_PATHS(0); break;
+        case 1: CPD_WALK_PATHS(1); break;
+        case 2: CPD_WALK_PATHS(2); break;
+        case 3: CPD_WALK_PATHS(3); break;
+        default: CPD_WALK_PATHS(4); break;
+    }
+#undef CPD_WALK_PATHS
+}
+
+void launch_table_paths_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                              uint32_t npad, uint32_t lb, const uint32_t* qs, const uint32_t* qt,
+                              const uint32_t* qrow, const uint32_t* qperm, const uint64_t* poff,
+                              const uint32_t* node_of_col, uint32_t nq, int32_t kmoves, uint32_t n,
+                              uint32_t* nodes, hipStream_t s) {
+    const kern::DenseRows rows{dense, npad >> (5u - lb), kern::Tbl{lb}};
+    launch_walk_paths(reinterpret_cast<const uint2*>(adj), shift, rows, qs, qt, qrow, qperm, poff,
+                      node_of_col, nq, walk_limit(kmoves, n), nodes, kDenseWaves, 1024u, s,
+                      kDenseWpb);
+}
+
+void launch_table_paths(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                        const uint32_t* runs, const uint32_t* qs, const uint32_t* qt,
+                        const uint32_t* qrow, const uint32_t* qperm, const uint64_t* poff,
+                        const uint32_t* node_of_col, uint32_t nq, int32_t kmoves, uint32_t n,
+                        uint32_t* nodes, hipStream_t s) {
+    launch_walk_paths(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs}, qs,
+                      qt, qrow, qperm, poff, node_of_col, nq, walk_limit(kmoves, n), nodes,
+                      kRleWaves, 1u << 30, s, kRleWpb);
+}
+
+// Path offsets: lens[q] = hops[q] + 1 (caller order), lens[nq] = 0, then an
+// exclusive sum over the nq + 1 values (tmp: path_scan_bytes(nq) bytes).
+hipError_t path_scan_bytes(uint32_t nq, size_t* bytes) {
+    *bytes = 0;
+    return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (const uint64_t*)nullptr,
+                                            (uint64_t*)nullptr, (int)(nq + 1u), (hipStream_t)0);
+}
+
+hipError_t launch_path_offsets(void* tmp, size_t tmp_bytes, const uint32_t* hops, uint32_t nq,
+                         uint64_t* lens, uint64_t* poff, hipStream_t st) {
+    launch(kern::path_lens, dim3(nq / 256u + 1u), dim3(256), st, hops, nq, lens);
+    size_t b = tmp_bytes;
+    return hipcub::DeviceScan::ExclusiveSum(tmp, b, lens, poff, (int)(nq + 1u), st);
 }
 
 

@@ -239,6 +239,25 @@ void launch_table_search(const uint32_t* adj, uint32_t shift, const uint64_t* of
                          uint64_t* cost, uint32_t* hops, uint8_t* fin, unsigned long long* agg,
                          hipStream_t s);
 
+// Path extraction (cpd_query_paths) after a table-search launch gave hops (in
+// caller order here): poff[nq + 1] = exclusive sum of hops + 1 (lens: nq + 1
+// u64 of scratch; tmp: path_scan_bytes bytes; both return hipCUB's status), then the same walks once
+// more, storing path q's node ids (node_of_col[column]) at
+// nodes[poff[qperm[i]] ...] for sorted query i.
+hipError_t path_scan_bytes(uint32_t nq, size_t* bytes);
+hipError_t launch_path_offsets(void* tmp, size_t tmp_bytes, const uint32_t* hops, uint32_t nq,
+                         uint64_t* lens, uint64_t* poff, hipStream_t st);
+void launch_table_paths_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                              uint32_t npad, uint32_t lb, const uint32_t* qs, const uint32_t* qt,
+                              const uint32_t* qrow, const uint32_t* qperm, const uint64_t* poff,
+                              const uint32_t* node_of_col, uint32_t nq, int32_t kmoves, uint32_t n,
+                              uint32_t* nodes, hipStream_t s);
+void launch_table_paths(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                        const uint32_t* runs, const uint32_t* qs, const uint32_t* qt,
+                        const uint32_t* qrow, const uint32_t* qperm, const uint64_t* poff,
+                        const uint32_t* node_of_col, uint32_t nq, int32_t kmoves, uint32_t n,
+                        uint32_t* nodes, hipStream_t s);
+
 // CPD-heuristic search (cpd_kernels.hip "CPD-heuristic search"): one search
 // per query (sorted by target row, qrow as for table-search) over the dense
 // move rows (2^lb bits per column); adj_f / adj_w: packed adjacency with

@@ -5,6 +5,7 @@
 //             --workerid I --maxworker W --outdir D --alg {table-search|cpd-search}
 //             [--partition M] [--device G] [--fifo PATH] [--once]
 //             [--index auto|rle|dense] [--read-threads T] [--parse-threads P]
+//             [--paths]  (table-search only: also write every walk's nodes)
 //             [--verbose]  (per request on stderr: read+parse / prepare / compute)
 //
 // Creates its request FIFO, streams the CPD buckets this worker owns onto its
@@ -29,6 +30,11 @@
 // t_astar = the search passes alone (0 for table-search).  With "debug":
 // true in the config, per-query
 // results are written to <query file>.res ("s t cost moves finished").
+// With --paths (table-search only) every request is answered through
+// cpd_query_paths, and when the answer line arrives <query file>.paths holds
+// one line per query in file order, "s t finished n v0 v1 ... v(n-1)": the n
+// = moves + 1 nodes of the walk from v0 = s (written as .paths.tmp, renamed
+// into place).  The answer line is the same with and without it.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -89,6 +95,60 @@ static std::string read_all(const std::string& path) {
     return s;
 }
 
+// <query file>.paths: the walks' nodes, fetched and written in pieces of at
+// most ~64M nodes (host memory stays bounded however long the paths are)
+static void write_paths(cpd_index* ix, const std::string& qfile, const std::vector<uint32_t>& s,
+                        const std::vector<uint32_t>& t, const std::vector<uint64_t>& off) {
+    constexpr uint64_t kPiece = 64ull << 20;
+    const size_t nq = s.size();
+    std::vector<uint8_t> fin(nq);
+    if (cpd_query_fetch(ix, nullptr, nullptr, fin.data()) != CPD_OK)
+        throw std::runtime_error(cpd_last_error());
+    const std::string path = qfile + ".paths", tmp = path + ".tmp";
+    std::FILE* f = std::fopen(tmp.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    std::vector<uint32_t> nodes;
+    std::string out;
+    auto put = [&out](uint64_t v, char sep) {
+        char d[24];
+        int k = 0;
+        do d[k++] = (char)('0' + v % 10u); while (v /= 10u);
+        while (k) out.push_back(d[--k]);
+        out.push_back(sep);
+    };
+    bool ok = true;
+    for (size_t q0 = 0; q0 < nq && ok;) {
+        size_t q1 = q0 + 1;
+        while (q1 < nq && off[q1 + 1] - off[q0] <= kPiece) ++q1;
+        nodes.resize((size_t)(off[q1] - off[q0]));
+        if (cpd_query_paths_fetch(ix, (uint32_t)q0, (uint32_t)(q1 - q0), nodes.data()) != CPD_OK) {
+            std::fclose(f);
+            ::unlink(tmp.c_str());
+            throw std::runtime_error(cpd_last_error());
+        }
+        for (size_t q = q0; q < q1; ++q) {
+            const uint64_t len = off[q + 1] - off[q];
+            put(s[q], ' ');
+            put(t[q], ' ');
+            put(fin[q] == 1 ? 1u : 0u, ' ');
+            put(len, len ? ' ' : '\n');
+            const uint32_t* v = nodes.data() + (off[q] - off[q0]);
+            for (uint64_t i = 0; i < len; ++i) put(v[i], i + 1 < len ? ' ' : '\n');
+            if (out.size() >= (1u << 20)) {
+                ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
+                out.clear();
+            }
+        }
+        q0 = q1;
+    }
+    if (ok && !out.empty()) ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
+        ::unlink(tmp.c_str());
+        throw std::runtime_error("cannot write " + path);
+    }
+}
+
 static bool write_answer(const std::string& path, const std::string& line) {
     // process_query.send_remote mkfifo's the answer before writing the request
     // (process_query.py:72-73); tolerate a late mkfifo for up to 10 s
@@ -125,7 +185,11 @@ int main(int argc, char** argv) {
     if (inputs.empty() || method.empty() || key <= 0 || wid < 0 || W <= 0 || wid >= W) {
         std::fprintf(stderr,
                      "usage: fifo_auto --input X.xy [DIFF] --partmethod {div|mod} --partkey K "
-                     "--workerid I --maxworker W --outdir D --alg table-search|cpd-search\n");
+                     "--workerid I --maxworker W --outdir D --alg table-search|cpd-search\n"
+                     "       [--paths]  table-search only: answer through cpd_query_paths and "
+                     "write every\n"
+                     "                  walk's nodes to <query file>.paths, one line per query:\n"
+                     "                  s t finished n v0 ... v(n-1)\n");
         return 2;
     }
     // table-search (make_fifos.py:20) or the CPD-heuristic search
@@ -134,6 +198,12 @@ int main(int argc, char** argv) {
     if (alg != "table-search" && !search) {
         std::fprintf(stderr, "fifo_auto: --alg must be table-search or cpd-search (got '%s')\n",
                      alg.c_str());
+        return 2;
+    }
+    const bool paths = a.has("paths");
+    if (paths && search) {
+        std::fprintf(stderr, "fifo_auto: --paths needs --alg table-search (the paths of a "
+                             "cpd-search are not extracted)\n");
         return 2;
     }
     int mcode = cli::method_code(method);
@@ -419,6 +489,12 @@ int main(int argc, char** argv) {
                 if (ss.overflow)
                     std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
                                  (unsigned long long)ss.overflow);
+            } else if (paths) {
+                static std::vector<uint64_t> poff;
+                poff.resize(nq + 1);
+                rc = cpd_query_paths(ix, k_moves, poff.data(), &st);
+                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                write_paths(ix, qfile, s, t, poff);
             } else {
                 rc = cpd_query_run(ix, k_moves, &st);
                 if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());

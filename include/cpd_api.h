@@ -381,6 +381,38 @@ int  cpd_query_prepare(cpd_index* ix, const uint32_t* s, const uint32_t* t,
 int  cpd_query_run(cpd_index* ix, int32_t k_moves, cpd_query_stats* st);
 int  cpd_query_fetch(cpd_index* ix, uint64_t* cost, uint32_t* hops,
                      uint8_t* finished);
+/* The walks of the last cpd_query_prepare, with their nodes: the sequence the
+ * repeated graph_oracle::get_move [U] walk visits, which the reference's
+ * workers only sum up — and, with k_moves = k (process_query.py:153 k_moves,
+ * args.py -k: "extract the first k moves, then replan"), the node where the
+ * walk stopped.  Path q is s[q], then the node reached by each move:
+ * hops[q] + 1 node ids (.xy ids, not columns), ending at t[q] when
+ * finished[q], else at the node where the walk stopped (k_moves reached, a
+ * move naming no out-edge, or the n-move loop guard).  offsets: nq + 1 values
+ * in the CALLER's query order, offsets[0] = 0, offsets[q+1] - offsets[q] =
+ * hops[q] + 1; the nodes stay in HBM (4 * offsets[nq] bytes; CPD_E_OOM naming
+ * them when they do not fit — the index and the prepared queries stay usable)
+ * until the next prepare / run / paths call on ix.  Also does what
+ * cpd_query_run does (st, and cpd_query_fetch afterwards returns this walk's
+ * cost / hops / finished).  The nodes never depend on the weights
+ * (cpd_index_set_weights), only cost does.  This is always the table-search
+ * walk: the paths of a preceding cpd_query_search are NOT what it returns.
+ * Known limit, inherited from the walk kernel (cpd_query_run has it too): in
+ * a batch large enough for a wave's lanes to be refilled (more than 65536
+ * queries on a dense index, 524288 on an RLE one) a refilled lane takes one
+ * move before k_moves is checked, so with k_moves = 0 such a query reports
+ * hops = 1 and a 2-node path instead of 0 and [s]; k_moves >= 1 and < 0 are
+ * exact at every size, and hops, cost and the path always agree.
+ * When a device arena is committed the node buffer is carved from it; the
+ * arena never takes a buffer back, so each batch with more nodes than any
+ * before it on this index uses up that many more arena bytes until
+ * cpd_device_arena_release (what does not fit is allocated separately).     */
+int  cpd_query_paths(cpd_index* ix, int32_t k_moves, uint64_t* offsets /* nq+1 */,
+                     cpd_query_stats* st);
+/* Path nodes of queries [first, first + count) of the caller's order, back to
+ * back: offsets[first+count] - offsets[first] values.  CPD_E_ARG before any
+ * cpd_query_paths on the prepared queries, or for a range past nq.           */
+int  cpd_query_paths_fetch(cpd_index* ix, uint32_t first, uint32_t count, uint32_t* nodes);
 void cpd_index_free(cpd_index* ix);
 
 /* [gpu] CPD-heuristic search — fifo_auto's other algorithm family
