@@ -24,13 +24,14 @@ HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(SRC) \
              -Wall -Wno-unused-parameter
 LDLIBS    := -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib
 
-HOST_OBJS := $(BLD)/host_util.o $(BLD)/ch.o $(BLD)/ch_gpu.o $(BLD)/plan.o $(BLD)/cpd_gpu.o $(BLD)/cpd_io.o \
-             $(BLD)/cpd_switches.o
+HOST_OBJS := $(BLD)/host_util.o $(BLD)/ch.o $(BLD)/ch_gpu.o $(BLD)/plan.o $(BLD)/cpd_io.o \
+             $(BLD)/cpd_switches.o $(BLD)/cpd_device.o $(BLD)/cpd_graph.o $(BLD)/cpd_rows.o \
+             $(BLD)/cpd_index.o $(BLD)/cpd_search.o
 DEV_OBJS  := $(BLD)/cpd_kernels.o $(BLD)/ch_kernels.o
 TOOLS     := make_cpd_auto fifo_auto gen_distribute_conf gen_synth
 BINS      := $(addprefix bin/,$(TOOLS))
 HDRS      := include/cpd_api.h $(SRC)/cpd_internal.hpp $(SRC)/cpd_kernels.hpp $(SRC)/cpd_io.hpp \
-             $(SRC)/ch_kernels.hpp $(SRC)/cpd_switches.hpp
+             $(SRC)/ch_kernels.hpp $(SRC)/cpd_switches.hpp $(SRC)/cpd_gpu_internal.hpp
 
 # Build provenance: sha256 over the library's and tools' sources (sorted by
 # path, contents concatenated — cpd.src_sha() recomputes it from the shipped

@@ -83,8 +83,8 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t total) {
 //                                   list's node s and its (leaf) arcs
 //   up index u (ascending arcs)  -> a row of the compact up store (gather)
 //   column (down-sweep)          -> a final distance row (gather)
-constexpr uint32_t kLeafBit = 0x80000000u;
-constexpr uint32_t kL1Bit = 0x40000000u;
+// kLeafBit and kL1Bit are defined in cpd_kernels.hpp: the host builds the
+// lists with them.
 constexpr uint32_t kIdxMask = 0x3FFFFFFFu;
 
 __device__ __forceinline__ void min4(uint4& acc, const uint4 d, uint32_t w) {

@@ -40,6 +40,11 @@ struct NarrowRows {
 // (~0: none).  Two stores, one per batch slot, so batch k+1's up-sweep runs
 // beside batch k's down-sweep.
 
+// Closed-form encodings of the two lowest upward levels in arcs and
+// down-sweep node slots (see "Closed forms" in cpd_kernels.hip).
+constexpr uint32_t kLeafBit = 0x80000000u;
+constexpr uint32_t kL1Bit = 0x40000000u;
+
 // One CH sweep level: `count` node slots starting at `slot0` of the
 // level-ordered node list; count * slabs workgroups of 256 threads, one slab =
 // 1024 targets of the B-wide batch row, XCD-remapped (CPD_XCD=0: off).

@@ -80,7 +80,7 @@ def move_run_counts(mv, n, bits, chunk=1024):
 
 
 def hilbert_keys(x, y):
-    """libcpd's lane key (cpd_gpu.cpp hilbert_keys): the Hilbert index of each
+    """libcpd's lane key (cpd_graph.cpp hilbert_keys): the Hilbert index of each
     node's coordinates on a 2^16 x 2^16 grid over the bounding box."""
     x = np.asarray(x, np.int64)
     y = np.asarray(y, np.int64)
@@ -106,7 +106,7 @@ def hilbert_keys(x, y):
 
 def lane_of(g, order, targets):
     """The batch lane each caller target occupies when the graph has
-    coordinates (cpd_gpu.cpp upload_targets: lanes sorted by (Hilbert key,
+    coordinates (cpd_rows.cpp prepare_targets: lanes sorted by (Hilbert key,
     column)).  lane_of(...)[i] = lane of targets[i]."""
     t = np.asarray(targets, np.int64)
     keys = hilbert_keys(g.x, g.y)[t]

@@ -2,7 +2,7 @@
 rows and walks (each shipped kernel instantiation is
 reached by a default or fallback path that a GPU test covers).
 
-The switches are read once per process (cpd_kernels.hip / cpd_gpu.cpp), so
+The switches are read once per process (cpd_kernels.hip / cpd_switches.cpp), so
 each setting runs in a child process, one after another (never two on the
 GPU at once): build the rows of a synthetic road graph (4-bit sets, the
 narrow path) and of the degree-8 graph (8-bit sets), compare with the

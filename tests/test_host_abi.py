@@ -1,0 +1,44 @@
+"""The argument-checking paths of the GPU half of the C ABI (csrc/cpd_device,
+cpd_graph, cpd_rows, cpd_index, cpd_search .cpp) that return before any device
+work: error codes and cpd_last_error texts, checked by a stand-alone program
+(tests/host_abi_check.cpp) linked from those five sources built with
+-fsanitize=address,undefined.  The kernels' launchers and the error channel
+come from the built libcpd.so; no GPU is needed."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "distributed-oracle-search_amd")
+CSRC = os.path.join(PKG, "csrc")
+ROCM = os.environ.get("ROCM", "/opt/rocm")
+UNITS = ("cpd_device", "cpd_graph", "cpd_rows", "cpd_index", "cpd_search")
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    out = str(tmp_path_factory.mktemp("abi") / "host_abi_check")
+    subprocess.run([gxx, "-O1", "-g", "-std=c++17", "-fopenmp", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
+                    "-I", os.path.join(ROCM, "include"), "-I", CSRC, "-I", os.path.join(ROOT, "include"),
+                    *[os.path.join(CSRC, u + ".cpp") for u in UNITS],
+                    os.path.join(ROOT, "tests", "host_abi_check.cpp"), "-o", out,
+                    "-L", PKG, "-lcpd", "-Wl,-rpath," + PKG,
+                    "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(ROCM, "lib")],
+                   check=True, capture_output=True, timeout=600)
+    return out
+
+
+def test_argument_checks_under_sanitizers(harness):
+    p = subprocess.run([harness], capture_output=True, text=True, timeout=120)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0, p.stdout + p.stderr
+    lines = p.stdout.strip().splitlines()
+    assert lines[-1] == "0 failures"
+    assert len(lines) >= 18 and all(l.startswith("ok ") for l in lines[:-1])
+    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr
