@@ -54,7 +54,7 @@ EXPORTED = [
     "cpd_device_mem_info", "cpd_rows_move_words", "cpd_rows_export_moves",
     "cpd_index_append_moves", "cpd_device_arena", "cpd_device_arena_release", "cpd_batch_bytes",
     "cpd_rows_move_bits", "cpd_graph_move_bits", "cpd_bucket_bytes", "cpd_space_check",
-    "cpd_query_paths", "cpd_query_paths_fetch",
+    "cpd_query_paths", "cpd_query_paths_fetch", "cpd_query_search_paths",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
@@ -101,6 +101,11 @@ class SearchStats(C.Structure):
                 ("tables", C.c_int32), ("reruns", C.c_uint64), ("resumed", C.c_uint64),
                 ("restarted", C.c_uint64), ("wasted_expanded", C.c_uint64),
                 ("passes", C.c_uint32), ("capacity", C.c_uint32), ("capacity_last", C.c_uint32)]
+
+
+class SearchPathsInfo(C.Structure):
+    _fields_ = [("nodes", C.c_uint64), ("prefix_nodes", C.c_uint64),
+                ("prefix_bytes", C.c_uint64), ("paths_ms", C.c_double)]
 
 
 class KernelTime(C.Structure):
@@ -693,6 +698,58 @@ class Index:
         if nq:
             _check(lib.cpd_query_search_counters(self._h, _ptr(cnt, u32p)))
         return cost, plen, fin, cnt, {k: getattr(st, k) for k, _ in SearchStats._fields_}
+
+    def search_paths(self, s, t, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
+                     capacity=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,
+                     capacity_max=0, prefix_bytes=0):
+        """search() with the nodes of every route found (cpd_query_search_paths):
+        (offsets u64[nq + 1], nodes u32[offsets[-1]], cost, plen, finished,
+        counters[nq, 5], stats).  Path q is nodes[offsets[q]:offsets[q + 1]]:
+        the A* tree's chain from s[q] to the incumbent's node, then the CPD
+        walk from there to t[q]; no nodes when finished[q] != 1.  stats holds
+        the search's and, under "paths", nodes / prefix_nodes / prefix_bytes /
+        paths_ms.  prefix_bytes: the prefix pool's size (0 = automatic); too
+        small raises CpdError(CPD_E_OOM) naming the bytes needed, with the
+        search's results still fetchable (search_fetch)."""
+        self.prepare(s, t)
+        offsets, st = self.search_paths_run(hscale, fscale, k_moves, itrs, time_ns, capacity,
+                                            virtual_tick_ns, tables, workspace_frac,
+                                            capacity_max, prefix_bytes)
+        nodes = self.paths_fetch(0, len(s))
+        cost, plen, fin, cnt = self.search_fetch()
+        return offsets, nodes, cost, plen, fin, cnt, st
+
+    def search_paths_run(self, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
+                         capacity=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,
+                         capacity_max=0, prefix_bytes=0):
+        """cpd_query_search_paths on the prepared queries: (offsets u64[nq + 1],
+        stats).  The offsets are kept: paths_fetch sizes its buffers from them."""
+        self._path_offsets = None
+        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
+                       int(capacity), int(virtual_tick_ns), SEARCH_FORMS[tables],
+                       float(workspace_frac), int(capacity_max))
+        st = SearchStats()
+        info = SearchPathsInfo()
+        offsets = np.empty(self._nq + 1, np.uint64)
+        _check(lib.cpd_query_search_paths(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)),
+                                          _ptr(offsets, u64p), C.byref(st), C.byref(info)))
+        self._path_offsets = offsets.copy()
+        d = {k: getattr(st, k) for k, _ in SearchStats._fields_}
+        d["paths"] = {k: getattr(info, k) for k, _ in SearchPathsInfo._fields_}
+        return offsets, d
+
+    def search_fetch(self):
+        """(cost, plen, finished, counters[nq, 5]) of the last search on the
+        prepared queries (cpd_query_fetch + cpd_query_search_counters)."""
+        nq = self._nq
+        cost = np.empty(nq, np.uint64)
+        plen = np.empty(nq, np.uint32)
+        fin = np.empty(nq, np.uint8)
+        _check(lib.cpd_query_fetch(self._h, _ptr(cost, u64p), _ptr(plen, u32p), _ptr(fin, u8p)))
+        cnt = np.empty((nq, 5), np.uint32)
+        if nq:
+            _check(lib.cpd_query_search_counters(self._h, _ptr(cnt, u32p)))
+        return cost, plen, fin, cnt
 
     def __del__(self):
         if getattr(self, "_h", None):

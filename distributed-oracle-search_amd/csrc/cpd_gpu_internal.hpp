@@ -486,6 +486,13 @@ struct cpd_index {
     std::vector<uint64_t> poff_h;
     DevBuf<uint32_t> pnodes;
     bool paths_ready = false;
+    // search paths (cpd_query_search_paths), scratch of one call, freed when
+    // it returns (the cursor stays): the prefix pool and its cursor;
+    // per query (sorted order) the prefix's place and length, v* and lw(v*);
+    // the suffix walk's offset pairs and their index (search_path_plan)
+    DevBuf<uint32_t> spp_pool, spp_pn, spp_vcol, spp_vlw, spp_wperm;
+    DevBuf<unsigned long long> spp_top, spp_off;
+    DevBuf<uint64_t> spp_woff;
 };
 
 template <class F>

@@ -695,7 +695,7 @@ int cpd_query_paths_fetch(cpd_index* ix, uint32_t first, uint32_t count, uint32_
     return guarded([&] {
         CPD_REQUIRE(ix, CPD_E_ARG, "null index");
         CPD_REQUIRE(ix->paths_ready, CPD_E_ARG,
-                    "paths fetch: no cpd_query_paths on the prepared queries yet");
+                    "paths fetch: no cpd_query_paths / cpd_query_search_paths on the prepared queries yet");
         CPD_REQUIRE((uint64_t)first + count <= ix->nq, CPD_E_ARG,
                     "paths fetch: queries [" + std::to_string(first) + ", " +
                         std::to_string((uint64_t)first + count) + ") past the batch's " +

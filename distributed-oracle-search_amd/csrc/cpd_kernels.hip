@@ -16,6 +16,7 @@
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "cpd_kernels.hpp"
 #include "cpd_switches.hpp"
@@ -3516,6 +3517,7 @@ struct Lane {
     uint64_t ub, t0;
     uint32_t expanded, inserted, touched, updated, surplus;
     bool done, overflow, spilled;
+    uint32_t vcol, vlw;  // PATHS: the incumbent's column v* and the moves of its CPD walk
 };
 
 // Resumable overflow.  A search checks, before each
@@ -3542,6 +3544,39 @@ struct SearchSpill {
     unsigned long long cap;            // its size, words
 };
 constexpr uint32_t kSpillHead = 14;
+
+// Search paths (the PATHS form, cpd_query_search_paths; DESIGN.md §3 "Search
+// paths").  The incumbent is "the A* tree from s to the node v* whose
+// expansion last lowered it, then the row's CPD walk from v* to t"; PATHS
+// keeps what names that route.  The lane's block gains par[2C] after its
+// other arrays: per hash slot the column whose relaxation last set the
+// slot's g (kNoCol for s; a slot that was only walked holds nothing
+// meaningful and is never read) — written where g is written, so every
+// assignment is a strict decrease of g and the chain v* -> par -> ... -> s is
+// a tree path.  The lane keeps v* and lw(v*) beside ub / best_len.  A spilled
+// search carries v* in the head's last word (0 without PATHS) and each
+// column's parent as one more word per entry (6 / 10 instead of 5 / 9);
+// lw(v*) is read back from the row's table or the column's memo.  A search
+// that ends for good with an incumbent follows the chain once to count it
+// (one hash probe per step), reserves that many u32 in the prefix pool with
+// one 64-bit atomicAdd (the spill pool's pattern) and, if the reservation
+// fits, follows it again storing the columns s ... v* in path order; the
+// cursor counts on when it does not fit, so the host learns the size needed.
+// Per query: the prefix's offset and length, v* and lw(v*) (t and 0 when
+// there is no path) — the suffix is table_walk_paths from v*.
+constexpr uint32_t kNoCol = 0xFFFFFFFFu;
+struct SearchPaths {
+    uint32_t* pool;              // prefix columns
+    unsigned long long* top;     // its cursor, u32 entries; runs on across passes
+    unsigned long long cap;      // its size, entries
+    unsigned long long* poff;    // [nq] the prefix's first entry
+    uint32_t* pn;                // [nq] its length (0: no path)
+    uint32_t* vcol;              // [nq] v*  (t: no path)
+    uint32_t* vlw;               // [nq] lw(v*)
+};
+struct NoSearchPaths {};
+template <bool PATHS>
+using SearchPathsArg = std::conditional_t<PATHS, SearchPaths, NoSearchPaths>;
 
 // The lane's workspace (one slot's arrays).
 struct LaneWs {
@@ -3697,7 +3732,7 @@ struct SearchTables {
     uint32_t n;
 };
 
-template <int SHIFT, bool TABLES>
+template <int SHIFT, bool TABLES, bool PATHS>
 // (one wave per SIMD: the register budget of 512 leaves the children arrays in
 // registers; 1024 one-wave workgroups fill the 1024 SIMDs)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void cpd_search(
@@ -3707,7 +3742,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const uint32_t* __restrict__ qt, const uint32_t* __restrict__ qrow, uint32_t nq,
     uint32_t chunk, SearchOpt opt, SearchWs ws, SearchSpill sp, uint64_t* __restrict__ cost_out,
     uint32_t* __restrict__ plen_out, uint8_t* __restrict__ fin_out,
-    uint32_t* __restrict__ qstats, unsigned long long* __restrict__ agg) {
+    uint32_t* __restrict__ qstats, unsigned long long* __restrict__ agg,
+    SearchPathsArg<PATHS> pp) {
     constexpr uint32_t KD = 1u << SHIFT;  // most new columns / heap entries of one expansion
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -3731,6 +3767,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                    reinterpret_cast<uint4*>(lb0) + (kHeapK - 1u),
                    TABLES ? nullptr : reinterpret_cast<uint4*>(lb0 + CH * 16ull + C2 * 40ull), C,
                    2u * C - 1u, Tbl{lb}};
+    // PATHS: par[2C] after the block's other arrays (aux ends the tables
+    // form's, stk the walks form's)
+    [[maybe_unused]] uint32_t* __restrict__ par = nullptr;
+    if constexpr (PATHS)
+        par = reinterpret_cast<uint32_t*>(lb0 + CH * 16ull + C2 * (TABLES ? 24ull : 48ull));
     unsigned long long s_exp = 0, s_ins = 0, s_tou = 0, s_upd = 0, s_sur = 0, s_len = 0,
                        s_fin = 0, s_ovf = 0;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
@@ -3757,6 +3798,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         L.done = false;
         L.overflow = false;
         L.spilled = false;
+        if constexpr (PATHS) {
+            L.vcol = kNoCol;
+            L.vlw = 0;
+        }
         L.t0 = __builtin_amdgcn_s_memrealtime();
         row = dense + (size_t)qrow[q] * wpr;
         rb = (size_t)qrow[q] * tb.n;
@@ -3774,7 +3819,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             L.t0 -= u64of(r[10], r[11]);
             const uint32_t ne = r[12];
             const uint32_t* __restrict__ h = r + kSpillHead;
-            constexpr uint32_t per = TABLES ? 5u : 9u;
+            constexpr uint32_t per = (TABLES ? 5u : 9u) + (PATHS ? 1u : 0u);
             const uint32_t* __restrict__ en = h + 3ull * L.hsize;
             for (uint32_t k = 0; k < ne; ++k) {
                 const uint32_t* __restrict__ o = en + (size_t)per * k;
@@ -3783,6 +3828,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 W.ent[i] = make_uint4(L.tag, o[0], o[1], o[2]);
                 W.aux[i] = make_uint2(o[3], o[4]);
                 if (!TABLES) W.memo[i] = make_uint4(o[5], o[6], o[7], o[8]);
+                if constexpr (PATHS) par[i] = o[per - 1u];
+            }
+            if constexpr (PATHS) {  // the incumbent node; its moves from the table / its memo
+                L.vcol = L.ub != kInf64 ? r[13] : kNoCol;
+                if (L.vcol != kNoCol) {
+                    if (TABLES) {
+                        L.vlw = tb.lrow[rb + L.vcol];
+                    } else {
+                        bool f;
+                        L.vlw = W.aux[hprobe(W.ent, W.mask, L.tag, L.vcol, f)].y & 0x3FFFFFFFu;
+                    }
+                }
             }
             // the heap after the hash: its entries' slots in this workspace
             for (uint32_t i = 0; i < L.hsize; ++i) {
@@ -3815,6 +3872,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             W.ent[si].w = 0u;
             W.aux[si].x = 0u;
             L.inserted = 1;
+            if constexpr (PATHS) par[si] = kNoCol;
             heap_push(W.hk, L.hsize, hkey_make(hval(opt, hs), L.s, si));
         }
     };
@@ -3823,7 +3881,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // search then restarts from scratch at the next capacity)
     auto spill = [&]() -> bool {
         if (!sp.rout) return false;
-        constexpr uint32_t per = TABLES ? 5u : 9u;
+        constexpr uint32_t per = (TABLES ? 5u : 9u) + (PATHS ? 1u : 0u);
         const unsigned long long words =
             kSpillHead + 3ull * L.hsize + (unsigned long long)per * L.used;
         const unsigned long long off = atomicAdd(sp.top, words);
@@ -3855,6 +3913,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 o[7] = mm.z;
                 o[8] = mm.w;
             }
+            if constexpr (PATHS) o[per - 1u] = par[i];
         }
         const uint64_t el = __builtin_amdgcn_s_memrealtime() - L.t0;
         r[0] = L.hsize;
@@ -3870,7 +3929,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         r[10] = (uint32_t)el;
         r[11] = (uint32_t)(el >> 32);
         r[12] = k;
-        r[13] = 0u;
+        if constexpr (PATHS) r[13] = L.vcol;
+        else r[13] = 0u;
         sp.at[L.q] = off;
         return true;
     };
@@ -3908,6 +3968,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 s_len += found ? L.best_len : 0u;
                 s_fin += found ? 1u : 0u;
                 s_ovf += L.overflow ? 1u : 0u;
+                if constexpr (PATHS) {
+                    // the prefix s ... v* of a search that ends here with an
+                    // incumbent: counted, reserved, then stored in path order.
+                    // A chain reaches s within `used` steps over columns of
+                    // this search; the bound and the hash-miss exit are
+                    // defensive (only a corrupted par could meet them) and
+                    // give the query no path (pn = 0) instead of a cut one.
+                    uint32_t cnt = 0;
+                    unsigned long long off = 0;
+                    if (found) {
+                        uint32_t c = L.vcol;
+                        for (; c != kNoCol && cnt < L.used; ++cnt) {
+                            bool f;
+                            const uint32_t i = hprobe(W.ent, W.mask, L.tag, c, f);
+                            if (!f) break;
+                            c = par[i];
+                        }
+                        if (c != kNoCol) cnt = 0;  // not a chain to s
+                        if (cnt) off = atomicAdd(pp.top, (unsigned long long)cnt);
+                        if (cnt && off + cnt <= pp.cap) {
+                            uint32_t k = cnt;
+                            for (uint32_t c = L.vcol; c != kNoCol && k;) {
+                                pp.pool[off + --k] = c;
+                                bool f;
+                                const uint32_t i = hprobe(W.ent, W.mask, L.tag, c, f);
+                                if (!f) break;
+                                c = par[i];
+                            }
+                        }
+                    }
+                    pp.poff[L.q] = off;
+                    pp.pn[L.q] = cnt;
+                    pp.vcol[L.q] = cnt ? L.vcol : L.t;
+                    pp.vlw[L.q] = cnt ? L.vlw : 0u;
+                }
             }
             if (take) {
                 const uint32_t nqi = next + (uint32_t)__builtin_popcountll(m & lt_mask);
@@ -4038,6 +4133,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 if (cand < L.ub) {
                     L.ub = cand;
                     L.best_len = dv + lw;
+                    if constexpr (PATHS) {
+                        L.vcol = v;
+                        L.vlw = lw;
+                    }
                 }
             }
         }
@@ -4096,6 +4195,7 @@ if (SHIFT <= 2) {
                 W.ent[ui].z = (uint32_t)ng;
                 W.ent[ui].w = (uint32_t)(ng >> 32);
                 W.aux[ui].x = dv + 1u;
+                if constexpr (PATHS) par[ui] = v;
                 wr[k] = ui;
                 ++L.inserted;
                 pv[k] = true;
@@ -4109,6 +4209,7 @@ if (SHIFT <= 2) {
                 W.ent[ui].z = (uint32_t)ng;
                 W.ent[ui].w = (uint32_t)(ng >> 32);
                 W.aux[ui].x = dv + 1u;
+                if constexpr (PATHS) par[ui] = v;
                 wr[k] = ui;
                 ++L.updated;
                 const uint64_t hu = TABLES ? hr[k] : u64of(W.memo[ui].x, W.memo[ui].y);
@@ -4157,6 +4258,7 @@ if (SHIFT <= 2) {
                 W.ent[ui].z = (uint32_t)ng;
                 W.ent[ui].w = (uint32_t)(ng >> 32);
                 W.aux[ui].x = dv + 1u;
+                if constexpr (PATHS) par[ui] = v;
                 ++L.inserted;
                 heap_push(W.hk, L.hsize, hkey_make(ng + hval(opt, hu), u, ui));
             } else if (ng < u64of(W.ent[ui].z, W.ent[ui].w)) {
@@ -4167,6 +4269,7 @@ if (SHIFT <= 2) {
                 W.ent[ui].z = (uint32_t)ng;
                 W.ent[ui].w = (uint32_t)(ng >> 32);
                 W.aux[ui].x = dv + 1u;
+                if constexpr (PATHS) par[ui] = v;
                 ++L.updated;
                 const uint64_t hu = TABLES ? tb.hrow[rb + u]
                                            : u64of(W.memo[ui].x, W.memo[ui].y);
@@ -4185,6 +4288,65 @@ if (SHIFT <= 2) {
     if (lane == 0)
 #pragma unroll
         for (int i = 0; i < 8; ++i) atomicAdd(&agg[i], v8[i]);
+}
+
+// Search paths, after the last pass (queries in sorted order, i; c = qperm[i]
+// the caller's index).  Path c = the prefix (pn nodes, s ... v*) and the CPD
+// walk from v* without its first node (lw more): pn + lw nodes, 0 without a
+// path.  search_path_lens: those counts in the caller's order, for the
+// exclusive sum (nq + 1 values; the last only closes it).
+__global__ __launch_bounds__(256) void search_path_lens(const uint32_t* __restrict__ pn,
+                                                        const uint32_t* __restrict__ vlw,
+                                                        const uint32_t* __restrict__ qperm,
+                                                        uint32_t nq, uint64_t* __restrict__ lens) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i > nq) return;
+    if (i == nq) {
+        lens[nq] = 0u;
+        return;
+    }
+    lens[qperm[i]] = pn[i] ? (uint64_t)pn[i] + vlw[i] : 0u;
+}
+
+// The suffix is table_walk_paths from v*, which writes walk i at
+// nodes[woff[wperm[i]] .. woff[wperm[i] + 1]): a pair of offsets of its own
+// per query (wperm[i] = 2 i) puts the walk's lw + 1 nodes at the END of path
+// c, its first node v* on the prefix's last place — v* is stored once, by
+// the walk.  A query without a path walks from t (no move) into no room.
+__global__ __launch_bounds__(256) void search_path_plan(const uint32_t* __restrict__ pn,
+                                                        const uint32_t* __restrict__ vlw,
+                                                        const uint32_t* __restrict__ qperm,
+                                                        const uint64_t* __restrict__ off,
+                                                        uint32_t nq, uint64_t* __restrict__ woff,
+                                                        uint32_t* __restrict__ wperm) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= nq) return;
+    const uint64_t o = off[qperm[i]];
+    const uint32_t p = pn[i];
+    woff[2ull * i] = p ? o + p - 1u : o;
+    woff[2ull * i + 1u] = p ? o + p + vlw[i] : o;
+    wperm[i] = 2u * i;
+}
+
+// The prefix without v* (pn - 1 columns of the pool) to the front of path c,
+// as node ids: a wave per query, a lane per node.
+__global__ __launch_bounds__(256) void search_path_join(const uint32_t* __restrict__ pool,
+                                                        const unsigned long long* __restrict__ poff,
+                                                        const uint32_t* __restrict__ pn,
+                                                        const uint32_t* __restrict__ qperm,
+                                                        const uint64_t* __restrict__ off,
+                                                        const uint32_t* __restrict__ node_of_col,
+                                                        uint32_t nq, uint32_t* __restrict__ nodes) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < nq;
+         i += waves) {
+        const uint32_t p = pn[i];
+        if (p < 2u) continue;
+        const uint32_t* __restrict__ src = pool + poff[i];
+        uint32_t* __restrict__ dst = nodes + off[qperm[i]];
+        for (uint32_t k = lane; k < p - 1u; k += 64u) dst[k] = node_of_col[src[k]];
+    }
 }
 
 }  // namespace kern
@@ -4659,7 +4821,7 @@ void launch_cpd_search(const uint32_t* adj_f, const uint32_t* adj_w, uint32_t sh
                        uint64_t time_ns, uint64_t tick_ns, void* ws, uint32_t cap,
                        uint32_t slots, const SearchSpillArgs& spill, uint64_t* cost,
                        uint32_t* plen, uint8_t* fin, uint32_t* qstats, unsigned long long* agg,
-                       hipStream_t s) {
+                       hipStream_t s, const SearchPathsArgs* paths) {
     const bool tables = hrow != nullptr;
     // Few searches left (a late pass): fewer lanes per wave, more waves —
     // each wave issues for fewer divergent lanes, and the SIMDs a full-wave
@@ -4679,7 +4841,7 @@ void launch_cpd_search(const uint32_t* adj_f, const uint32_t* adj_w, uint32_t sh
     // lane-major blocks: search_ws_bytes_per_slot each, 128-B aligned; the
     // heap first
     w.base = static_cast<char*>(ws);
-    w.stride = search_ws_bytes_per_slot(cap, tables);
+    w.stride = search_ws_bytes_per_slot(cap, tables, paths != nullptr);
     w.lpw = lpw;
     const kern::SearchOpt o{hscale, fscale, kmoves, itrs, time_ns, tick_ns};
     const kern::SearchTables tb{hrow, crow, lrow, n};
@@ -4693,12 +4855,18 @@ void launch_cpd_search(const uint32_t* adj_f, const uint32_t* adj_w, uint32_t sh
     const uint2* af = reinterpret_cast<const uint2*>(adj_f);
     const uint2* aw = reinterpret_cast<const uint2*>(adj_w);
     const uint32_t wpr = npad >> (5u - lb);
-#define CPD_SEARCH(SH, T)                                                                    \
-    launch(kern::cpd_search<SH, T>, grid, blk, s, af, aw, dense, wpr, lb, tb, qs, qt, qrow, nq, c2, \
-           o, w, sp, cost, plen, fin, qstats, agg)
-#define CPD_SEARCH_T(SH)          \
-    if (tables) CPD_SEARCH(SH, true); \
-    else CPD_SEARCH(SH, false)
+    kern::SearchPaths pp{};
+    if (paths)
+        pp = kern::SearchPaths{paths->pool, paths->top, paths->cap, paths->poff, paths->pn,
+                               paths->vcol, paths->vlw};
+#define CPD_SEARCH(SH, T, P, PP)                                                              \
+    launch(kern::cpd_search<SH, T, P>, grid, blk, s, af, aw, dense, wpr, lb, tb, qs, qt, qrow, nq, \
+           c2, o, w, sp, cost, plen, fin, qstats, agg, PP)
+#define CPD_SEARCH_T(SH)                                                   \
+    if (paths && tables) CPD_SEARCH(SH, true, true, pp);                   \
+    else if (paths) CPD_SEARCH(SH, false, true, pp);                       \
+    else if (tables) CPD_SEARCH(SH, true, false, kern::NoSearchPaths{});   \
+    else CPD_SEARCH(SH, false, false, kern::NoSearchPaths{})
     switch (shift) {
         case 0: CPD_SEARCH_T(0); break;
         case 1: CPD_SEARCH_T(1); break;
@@ -4769,17 +4937,45 @@ void launch_scatter_u8(const uint8_t* in, const uint32_t* perm, uint32_t nq, uin
 // Workspace per lane slot and column of capacity: hash entries 2 x (16 + 8),
 // heap 16 (f, column, hash slot), and for memoised walks the memo (2 x 16)
 // and walk stack (16).  Per slot: ent 32C, aux 16C (+ memo 32C, stk 16C with
-// walks) and the heap, 16 (C + kHeapK) B; a multiple of 128 B (aligned
-// lane-major blocks)
-uint64_t search_ws_bytes_per_slot(uint32_t cap, bool tables) {
-    const uint64_t b = (tables ? 64ull : 112ull) * cap + 16ull * kern::kHeapK;
+// walks), the heap, 16 (C + kHeapK) B, and with paths par, 8C, last; a
+// multiple of 128 B (aligned lane-major blocks)
+uint64_t search_ws_bytes_per_slot(uint32_t cap, bool tables, bool paths) {
+    const uint64_t per = (tables ? 64ull : 112ull) + (paths ? 8ull : 0ull);
+    const uint64_t b = per * cap + 16ull * kern::kHeapK;
     return (b + 127u) / 128u * 128u;
 }
 
 // a record: the head, <= cap heap entries of 3 words, <= cap columns of 5
-// (tables) or 9 (walks) words
-uint64_t search_spill_words(uint32_t cap, bool tables) {
-    return kern::kSpillHead + (tables ? 8ull : 12ull) * cap;
+// (tables) or 9 (walks) words, one more each with paths (the parent)
+uint64_t search_spill_words(uint32_t cap, bool tables, bool paths) {
+    return kern::kSpillHead + (tables ? 8ull : 12ull) * cap + (paths ? 1ull : 0ull) * cap;
+}
+
+hipError_t launch_search_path_offsets(void* tmp, size_t tmp_bytes, const uint32_t* pn,
+                                      const uint32_t* vlw, const uint32_t* qperm, uint32_t nq,
+                                      uint64_t* lens, uint64_t* off, hipStream_t st) {
+    launch(kern::search_path_lens, dim3(nq / 256u + 1u), dim3(256), st, pn, vlw, qperm, nq, lens);
+    size_t b = tmp_bytes;
+    return hipcub::DeviceScan::ExclusiveSum(tmp, b, lens, off, (int)(nq + 1u), st);
+}
+
+void launch_search_path_plan(const uint32_t* pn, const uint32_t* vlw, const uint32_t* qperm,
+                             const uint64_t* off, uint32_t nq, uint64_t* woff, uint32_t* wperm,
+                             hipStream_t st) {
+    if (!nq) return;
+    launch(kern::search_path_plan, dim3((nq + 255u) / 256u), dim3(256), st, pn, vlw, qperm, off, nq,
+           woff, wperm);
+}
+
+void launch_search_path_join(const uint32_t* pool, const unsigned long long* poff,
+                             const uint32_t* pn, const uint32_t* qperm, const uint64_t* off,
+                             const uint32_t* node_of_col, uint32_t nq, uint32_t* nodes,
+                             hipStream_t st) {
+    if (!nq) return;
+    // four waves a workgroup, a query a wave; at most 16k workgroups, striding
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)nq + 3u) / 4u, 16384u);
+    launch(kern::search_path_join, dim3(blocks), dim3(256), st, pool, poff, pn, qperm, off,
+           node_of_col, nq, nodes);
 }
 
 }  // namespace cpd

@@ -283,7 +283,7 @@ void launch_search_tables(const uint32_t* dense, uint32_t npad, uint32_t lb, con
 // Lane slots the search launches for nq queries (a multiple of 64); the
 // workspace holds search_ws_bytes_per_slot(cap, tables) bytes per slot.
 uint32_t search_slots(uint32_t nq);
-uint64_t search_ws_bytes_per_slot(uint32_t cap, bool tables);
+uint64_t search_ws_bytes_per_slot(uint32_t cap, bool tables, bool paths = false);
 // Resumable overflow (cpd_kernels.hip "Resumable overflow"): a search that
 // would outgrow its workspace stops before the pop and, when rout is set,
 // copies its state into that pool (a record of at most
@@ -299,7 +299,21 @@ struct SearchSpillArgs {
     unsigned long long* top = nullptr;
     unsigned long long cap_words = 0;
 };
-uint64_t search_spill_words(uint32_t cap, bool tables);
+uint64_t search_spill_words(uint32_t cap, bool tables, bool paths = false);
+// Search paths (cpd_kernels.hip "Search paths"): with `paths` the launch is
+// the PATHS form — the workspace and the records of the sizes the two
+// functions above give for paths = true — and every search that ends for good
+// with an incumbent stores its prefix, the columns s ... v*, in `pool` (cap
+// u32 entries; *top bumps across the passes and counts on past cap, nothing
+// stored then) and per query poff / pn (the prefix's place and length; pn 0:
+// no path), vcol / vlw (v* and the moves of its CPD walk; t and 0: no path).
+struct SearchPathsArgs {
+    uint32_t* pool = nullptr;
+    unsigned long long* top = nullptr;
+    unsigned long long cap = 0;
+    unsigned long long* poff = nullptr;
+    uint32_t *pn = nullptr, *vcol = nullptr, *vlw = nullptr;
+};
 void launch_cpd_search(const uint32_t* adj_f, const uint32_t* adj_w, uint32_t shift,
                        const uint32_t* dense, uint32_t npad, uint32_t lb, const uint64_t* hrow,
                        const uint64_t* crow, const uint32_t* lrow, uint32_t n,
@@ -308,6 +322,23 @@ void launch_cpd_search(const uint32_t* adj_f, const uint32_t* adj_w, uint32_t sh
                        uint64_t time_ns, uint64_t tick_ns, void* ws, uint32_t cap,
                        uint32_t slots, const SearchSpillArgs& spill, uint64_t* cost,
                        uint32_t* plen, uint8_t* fin, uint32_t* qstats, unsigned long long* agg,
-                       hipStream_t s);
+                       hipStream_t s, const SearchPathsArgs* paths = nullptr);
+// Search paths after the last pass (queries in sorted order; qperm to the
+// caller's): off[nq + 1] = exclusive sum of pn + vlw (0 without a path) in
+// the caller's order (lens: nq + 1 u64 of scratch; tmp: path_scan_bytes);
+// plan: the offset pairs woff[2 nq] and wperm[nq] with which
+// launch_table_paths_dense, given vcol as the sources, writes each walk at
+// the end of its path; join: the prefixes (without v*) to the front, as
+// node ids.
+hipError_t launch_search_path_offsets(void* tmp, size_t tmp_bytes, const uint32_t* pn,
+                                      const uint32_t* vlw, const uint32_t* qperm, uint32_t nq,
+                                      uint64_t* lens, uint64_t* off, hipStream_t st);
+void launch_search_path_plan(const uint32_t* pn, const uint32_t* vlw, const uint32_t* qperm,
+                             const uint64_t* off, uint32_t nq, uint64_t* woff, uint32_t* wperm,
+                             hipStream_t st);
+void launch_search_path_join(const uint32_t* pool, const unsigned long long* poff,
+                             const uint32_t* pn, const uint32_t* qperm, const uint64_t* off,
+                             const uint32_t* node_of_col, uint32_t nq, uint32_t* nodes,
+                             hipStream_t st);
 
 }  // namespace cpd

@@ -109,6 +109,12 @@ struct SearchPasses {
     const uint32_t* adj_w;
     const bool tables;
     const double wfrac;
+    // paths: the PATHS form of the kernel (cpd_query_search_paths) — par in
+    // the workspace and the records, every search's prefix into ix->spp_pool
+    // (pool_entries u32, allocated by the caller before the first pass is
+    // sized: avail() then sees what is left)
+    const bool paths;
+    const uint64_t pool_entries;
     hipStream_t sm;
     uint32_t cap_max, cap;
     uint64_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -122,6 +128,10 @@ struct SearchPasses {
     DevBuf<uint64_t> d_cost;
     DevBuf<uint8_t> d_fin;
     DevBuf<unsigned long long> d_agg, d_res;
+    // paths: the pass's prefix records (pass >= 2; pass 1: the index's own)
+    DevBuf<unsigned long long> d_poff;
+    DevBuf<uint32_t> d_pn, d_vcol, d_vlw;
+    SearchPathsArgs pa;
     int pin = 0;                              // spool[pin]: the records the pass resumes from
     bool have_resume = false;
     // the pass being run (size_pass): its inputs and outputs, lanes, spill pool
@@ -136,9 +146,9 @@ struct SearchPasses {
     unsigned long long hp[8];                 // the pass's sums (launch_pass)
 
     SearchPasses(cpd_index* index, const cpd_search_opts& opts, const uint32_t* adj, bool tab,
-                 double frac)
-        : ix(index), g(index->g), o(opts), adj_w(adj), tables(tab), wfrac(frac), sm(g->stream),
-          m(index->nq) {
+                 double frac, bool with_paths = false, uint64_t pool = 0)
+        : ix(index), g(index->g), o(opts), adj_w(adj), tables(tab), wfrac(frac),
+          paths(with_paths), pool_entries(pool), sm(g->stream), m(index->nq) {
         const bool auto_cap = o.capacity == 0;
         cap_max = o.capacity_max ? o.capacity_max
                   : auto_cap     ? pow2_at_least(4ull * std::max(g->n, 16u))
@@ -148,6 +158,13 @@ struct SearchPasses {
         ix->qstats.alloc(5ull * std::max(1u, m));
         ix->sagg.alloc(8);
         ix->stop.alloc(1);
+        if (paths) {
+            for (DevBuf<uint32_t>* b : {&ix->spp_pn, &ix->spp_vcol, &ix->spp_vlw})
+                b->alloc(std::max(1u, m));
+            ix->spp_off.alloc(std::max(1u, m));
+            ix->spp_top.alloc(1);
+            HIP_CHECK(hipMemsetAsync(ix->spp_top.p, 0, sizeof(unsigned long long), sm));
+        }
     }
 
     // HBM the passes may use: what is free plus what this index's search
@@ -166,7 +183,7 @@ struct SearchPasses {
         uint32_t c = std::min(o.fscale > 0.0 && tables ? (1u << 13) : (1u << 14), cap_max);
         const size_t budget = (size_t)(wfrac * (double)avail(0) * (c < cap_max ? 0.75 : 1.0));
         const uint64_t lanes = m ? search_slots(m) : 64u;
-        while (c > (1u << 10) && lanes * search_ws_bytes_per_slot(c, tables) > budget) c >>= 1;
+        while (c > (1u << 10) && lanes * search_ws_bytes_per_slot(c, tables, paths) > budget) c >>= 1;
         return c;
     }
 
@@ -183,13 +200,21 @@ struct SearchPasses {
         p_fin = first ? ix->fin.p : d_fin.p;
         p_st = first ? ix->qstats.p : d_st.p;
         p_agg = first ? ix->sagg.p : d_agg.p;
+        if (paths)
+            pa = SearchPathsArgs{ix->spp_pool.p,
+                                 ix->spp_top.p,
+                                 pool_entries,
+                                 first ? ix->spp_off.p : d_poff.p,
+                                 first ? ix->spp_pn.p : d_pn.p,
+                                 first ? ix->spp_vcol.p : d_vcol.p,
+                                 first ? ix->spp_vlw.p : d_vlw.p};
         // lanes: as many as the workspace share holds (whole waves),
         // leaving a quarter of it to the spill pool when a later pass
         // can resume; the pool takes the rest of the share
         const size_t live_in = have_resume ? ix->spool[pin].n * 4u : 0u;
         const size_t av = avail(live_in);
         const size_t share = (size_t)(wfrac * (double)av);
-        const size_t per_slot = search_ws_bytes_per_slot(cap, tables);
+        const size_t per_slot = search_ws_bytes_per_slot(cap, tables, paths);
         // (a quarter in pass 1, a tenth later: fewer searches spill again)
         const size_t ws_budget = more ? (first ? share / 4u * 3u : share / 10u * 9u) : share;
         const uint64_t fit = ws_budget / (64ull * per_slot);
@@ -206,10 +231,10 @@ struct SearchPasses {
             sa.rin = ix->spool[pin].p;
         }
         if (more) {
-            const uint64_t want = (uint64_t)m * search_spill_words(cap, tables);
+            const uint64_t want = (uint64_t)m * search_spill_words(cap, tables, paths);
             const uint64_t left = share > (size_t)slots * per_slot ? share - (size_t)slots * per_slot : 0;
             const uint64_t words = search_pool_words(std::min<uint64_t>(want, left / 4u));
-            if (words >= search_spill_words(cap, tables)) {
+            if (words >= search_spill_words(cap, tables, paths)) {
                 DevBuf<uint32_t>& out = ix->spool[pin ^ 1];
                 out.release();
                 out.alloc(words);
@@ -234,7 +259,7 @@ struct SearchPasses {
                           tables ? ix->hrow.p : nullptr, ix->crow.p, ix->lrow.p, g->n, pq_s, pq_t,
                           pq_r, m, o.hscale, o.fscale, o.k_moves, o.itrs, o.time_ns,
                           o.virtual_tick_ns, ix->sws.p, cap, slots, sa, p_cost, p_hops, p_fin,
-                          p_st, p_agg, sm);
+                          p_st, p_agg, sm, paths ? &pa : nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(ev.e[1], sm));
         if (!first) {  // this pass's results over the first pass's
@@ -242,6 +267,13 @@ struct SearchPasses {
             launch_scatter_u32(d_hops.p, d_idx.p, m, 1u, ix->hops.p, sm);
             launch_scatter_u8(d_fin.p, d_idx.p, m, ix->fin.p, sm);
             launch_scatter_u32(d_st.p, d_idx.p, m, 5u, ix->qstats.p, sm);
+            if (paths) {  // each query's prefix is the one of the pass it ended in
+                launch_scatter_u64(reinterpret_cast<const uint64_t*>(d_poff.p), d_idx.p, m,
+                                   reinterpret_cast<uint64_t*>(ix->spp_off.p), sm);
+                launch_scatter_u32(d_pn.p, d_idx.p, m, 1u, ix->spp_pn.p, sm);
+                launch_scatter_u32(d_vcol.p, d_idx.p, m, 1u, ix->spp_vcol.p, sm);
+                launch_scatter_u32(d_vlw.p, d_idx.p, m, 1u, ix->spp_vlw.p, sm);
+            }
         }
         HIP_CHECK(hipMemcpyAsync(hp, p_agg, sizeof hp, hipMemcpyDeviceToHost, sm));
         HIP_CHECK(hipStreamSynchronize(sm));
@@ -273,7 +305,7 @@ struct SearchPasses {
         const size_t av2 = avail(sa.rout ? ix->spool[pin ^ 1].n * 4u : 0u);
         const double share2 = wfrac * (double)av2;
         for (uint32_t c = std::min(cap * 4u, cap_max); c > cap; c >>= 1) {
-            const double per = (double)search_ws_bytes_per_slot(c, tables);
+            const double per = (double)search_ws_bytes_per_slot(c, tables, paths);
             if (64.0 * per > share2) continue;
             if (!next) next = c;
             if ((double)search_slots(left) * per <= 0.9 * share2) {
@@ -354,6 +386,12 @@ struct SearchPasses {
         d_cost.alloc(m2);
         d_fin.alloc(m2);
         d_agg.alloc(8);
+        if (paths) {
+            d_poff.alloc(m2);
+            d_pn.alloc(m2);
+            d_vcol.alloc(m2);
+            d_vlw.alloc(m2);
+        }
         have_resume = any_res;
         keep_spill_pool(any_res);
         m = m2;
@@ -410,6 +448,65 @@ void fill_search_stats(cpd_search_stats* st, const SearchPasses& p, uint32_t nq,
     st->capacity_last = p.cap_last;
 }
 
+// The automatic prefix pool (cpd_query_search_paths, prefix_bytes = 0): a
+// prefix is a simple path, so 4 n bytes per query always suffice; at most
+// 1/32 of the free HBM — the pool is taken before the workspace is sized, and
+// every byte of it is a byte fewer for lanes.  The share is a policy, not a
+// measured optimum: nobody has swept it.  What it cannot hold is reported
+// with the size to ask for.
+uint64_t auto_prefix_bytes(uint32_t nq, uint32_t n) {
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t bound = 4ull * std::max(1u, nq) * std::max(1u, n);
+    return std::max<uint64_t>(256u, std::min<uint64_t>(bound, free_b / 32u));
+}
+
+// cpd_query_search; with `paths` the PATHS form (cpd_query_search_paths),
+// its prefix pool of *pool_bytes (0: automatic; the size used comes back) —
+// returns the pool's cursor, the prefix nodes of all queries.
+uint64_t run_search(cpd_index* ix, const cpd_search_opts* opts, cpd_search_stats* st, bool paths,
+                    uint64_t* pool_bytes) {
+    cpd_search_opts o{1.0, 0.0, -1, -1, 0, 0, 0, CPD_SEARCH_AUTO, 0.0, 0};
+    if (opts) o = *opts;
+    const double wfrac = check_search_opts(ix, o);
+    cpd_graph* g = ix->g;
+    g->select();
+    const uint32_t nq = ix->nq;
+    if (!ix->dense_ready) ensure_dense(ix);
+    const uint32_t* adj_w = ix->custom_w ? ix->adj_sel.p : g->adj.p;
+    const bool tables = decide_tables(ix, o);
+    const double tables_ms = build_search_tables(ix, adj_w, tables);
+    uint64_t pool_entries = 0;
+    if (paths) {
+        // the pool at the size asked for, before the first pass is sized
+        ix->spp_pool.release();
+        if (!*pool_bytes) *pool_bytes = auto_prefix_bytes(nq, g->n);
+        pool_entries = *pool_bytes / 4u;
+        ix->spp_pool.alloc(pool_entries);
+    }
+    SearchPasses p(ix, o, adj_w, tables, wfrac, paths, pool_entries);
+    const uint32_t cap0 = p.cap;
+    while (p.m) {
+        p.size_pass();
+        p.launch_pass();
+        if (!p.hp[7] || !p.collect_reruns()) break;
+    }
+    // the spill pools are scratch: freed with the pass that used them
+    ix->spool[0].release();
+    ix->spool[1].release();
+    if (g->timing) {
+        Agg& ag = g->agg["cpd_search"];
+        ag.launches += p.passes;
+        ag.ms += p.ms;
+    }
+    ix->searched = true;
+    if (st) fill_search_stats(st, p, nq, cap0, tables_ms);
+    unsigned long long used = 0;
+    if (paths)
+        HIP_CHECK(hipMemcpy(&used, ix->spp_top.p, sizeof used, hipMemcpyDeviceToHost));
+    return used;
+}
+
 }  // namespace
 
 extern "C" {
@@ -417,33 +514,115 @@ extern "C" {
 int cpd_query_search(cpd_index* ix, const cpd_search_opts* opts, cpd_search_stats* st) {
     return guarded([&] {
         CPD_REQUIRE(ix, CPD_E_ARG, "null index");
-        cpd_search_opts o{1.0, 0.0, -1, -1, 0, 0, 0, CPD_SEARCH_AUTO, 0.0, 0};
-        if (opts) o = *opts;
-        const double wfrac = check_search_opts(ix, o);
-        cpd_graph* g = ix->g;
-        g->select();
+        run_search(ix, opts, st, false, nullptr);
+    });
+}
+
+int cpd_query_search_paths(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                           uint64_t* offsets, cpd_search_stats* st, cpd_search_paths_info* info) {
+    return guarded([&] {
+        CPD_REQUIRE(ix && offsets, CPD_E_ARG, "search paths: null argument");
         const uint32_t nq = ix->nq;
-        if (!ix->dense_ready) ensure_dense(ix);
-        const uint32_t* adj_w = ix->custom_w ? ix->adj_sel.p : g->adj.p;
-        const bool tables = decide_tables(ix, o);
-        const double tables_ms = build_search_tables(ix, adj_w, tables);
-        SearchPasses p(ix, o, adj_w, tables, wfrac);
-        const uint32_t cap0 = p.cap;
-        while (p.m) {
-            p.size_pass();
-            p.launch_pass();
-            if (!p.hp[7] || !p.collect_reruns()) break;
+        CPD_REQUIRE(nq < 0x7FFFFFFFu, CPD_E_RANGE, "search paths: too many queries for one batch");
+        ix->paths_ready = false;
+        if (info) *info = cpd_search_paths_info{0, 0, 0, 0.0};
+        // the prefix pool and the per-query records are scratch of this call:
+        // freed however it ends (as the spill pools are), so that a later
+        // search on the index is sized from the same HBM as before
+        struct Scratch {
+            cpd_index* ix;
+            ~Scratch() {
+                for (DevBuf<uint32_t>* b : {&ix->spp_pool, &ix->spp_pn, &ix->spp_vcol,
+                                            &ix->spp_vlw, &ix->spp_wperm})
+                    b->release();
+                ix->spp_off.release();
+                ix->spp_woff.release();
+            }
+        } scratch{ix};
+        uint64_t pool_bytes = prefix_bytes;
+        const uint64_t used = run_search(ix, opts, st, true, &pool_bytes);
+        if (info) {
+            info->prefix_nodes = used;
+            info->prefix_bytes = pool_bytes;
         }
-        // the spill pools are scratch: freed with the pass that used them
-        ix->spool[0].release();
-        ix->spool[1].release();
+        // the search's results are whole and fetchable from here on, whatever
+        // becomes of the paths
+        CPD_REQUIRE(used <= pool_bytes / 4u, CPD_E_OOM,
+                    "search paths: the prefixes need " + std::to_string(4ull * used) +
+                        " bytes of prefix pool, " + std::to_string(pool_bytes) +
+                        " were given: call again with prefix_bytes >= " +
+                        std::to_string(4ull * used));
+        if (!nq) {
+            offsets[0] = 0;
+            ix->poff_h.assign(1, 0);
+            ix->paths_ready = true;
+            return;
+        }
+        cpd_graph* g = ix->g;
+        hipStream_t s = g->stream;
+        if (!g->inv_d.p) g->inv_d.upload(g->inv.data(), g->n, s);
+        ix->plens.alloc((size_t)nq + 1u);
+        ix->poff.alloc((size_t)nq + 1u);
+        ix->spp_woff.alloc(2ull * nq);
+        ix->spp_wperm.alloc(nq);
+        size_t scan_bytes = 0;
+        HIP_CHECK(path_scan_bytes(nq, &scan_bytes));
+        ix->qsort_tmp.alloc(scan_bytes);
+        Events<4> ev(g);
+        // offsets: pn + lw(v*) per query in the caller's order, exclusive sum
+        HIP_CHECK(hipEventRecord(ev.e[0], s));
+        HIP_CHECK(launch_search_path_offsets(ix->qsort_tmp.p, ix->qsort_tmp.n, ix->spp_pn.p,
+                                             ix->spp_vlw.p, ix->qperm.p, nq, ix->plens.p,
+                                             ix->poff.p, s));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ev.e[1], s));
+        ix->poff_h.resize((size_t)nq + 1u);
+        HIP_CHECK(hipMemcpyAsync(ix->poff_h.data(), ix->poff.p, ((size_t)nq + 1u) * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        const uint64_t total = ix->poff_h[nq];
+        try {  // the index's path buffer (cpd_query_paths: from the arena when there is one)
+            ArenaScope carve;
+            ix->pnodes.alloc((size_t)total);
+        } catch (const Error& e) {
+            (void)hipGetLastError();
+            if (e.code != CPD_E_OOM) throw;
+            throw Error(CPD_E_OOM, "search paths: " + std::to_string(4ull * total) +
+                                       " bytes of HBM for " + std::to_string(total) +
+                                       " path nodes of " + std::to_string(nq) +
+                                       " queries do not fit");
+        }
+        // the suffixes: the table-search walk from every v* (k_moves < 0: to
+        // t) into the end of its path — over the dense rows the search
+        // itself used, with buffers of its own (the search's cost / hops /
+        // fin stay) — then the prefixes in front
+        HIP_CHECK(hipEventRecord(ev.e[2], s));
+        launch_search_path_plan(ix->spp_pn.p, ix->spp_vlw.p, ix->qperm.p, ix->poff.p, nq,
+                                ix->spp_woff.p, ix->spp_wperm.p, s);
+        launch_table_paths_dense(g->adj.p, g->adj_shift, ix->dense.p, g->npad, g->tlb,
+                                 ix->spp_vcol.p, ix->qt.p, ix->qrow.p, ix->spp_wperm.p,
+                                 ix->spp_woff.p, g->inv_d.p, nq, -1, g->n, ix->pnodes.p, s);
+        launch_search_path_join(ix->spp_pool.p, ix->spp_off.p, ix->spp_pn.p, ix->qperm.p,
+                                ix->poff.p, g->inv_d.p, nq, ix->pnodes.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ev.e[3], s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        float ms_off = 0.f, ms_fill = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms_off, ev.e[0], ev.e[1]));
+        HIP_CHECK(hipEventElapsedTime(&ms_fill, ev.e[2], ev.e[3]));
         if (g->timing) {
-            Agg& ag = g->agg["cpd_search"];
-            ag.launches += p.passes;
-            ag.ms += p.ms;
+            Agg& ag = g->agg["search_paths"];
+            ag.launches++;
+            ag.ms += ms_off + ms_fill;
+            // the walk's bytes are not modelled: nodes written, prefixes read
+            ag.bytes += 4.0 * (double)total + 4.0 * (double)used;
         }
-        ix->searched = true;
-        if (st) fill_search_stats(st, p, nq, cap0, tables_ms);
+        if (info) {
+            info->nodes = total;
+            info->paths_ms = (double)ms_off + (double)ms_fill;
+        }
+        std::memcpy(offsets, ix->poff_h.data(), ((size_t)nq + 1u) * sizeof(uint64_t));
+        ix->paths_ready = true;
     });
 }
 

@@ -6,6 +6,7 @@
 //             [--partition M] [--device G] [--fifo PATH] [--once]
 //             [--index auto|rle|dense] [--read-threads T] [--parse-threads P]
 //             [--paths]  (table-search only: also write every walk's nodes)
+//             [--search-paths]  (cpd-search only: also write every route's nodes)
 //             [--verbose]  (per request on stderr: read+parse / prepare / compute)
 //
 // Creates its request FIFO, streams the CPD buckets this worker owns onto its
@@ -35,6 +36,10 @@
 // one line per query in file order, "s t finished n v0 v1 ... v(n-1)": the n
 // = moves + 1 nodes of the walk from v0 = s (written as .paths.tmp, renamed
 // into place).  The answer line is the same with and without it.
+// With --search-paths (cpd-search only) every request is answered through
+// cpd_query_search_paths and <query file>.paths holds the search paths in
+// the same format: the A* tree's chain from s to the incumbent's node, then
+// the CPD walk to t; "s t 0 0" (no nodes) for a query without a route.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -189,7 +194,11 @@ int main(int argc, char** argv) {
                      "       [--paths]  table-search only: answer through cpd_query_paths and "
                      "write every\n"
                      "                  walk's nodes to <query file>.paths, one line per query:\n"
-                     "                  s t finished n v0 ... v(n-1)\n");
+                     "                  s t finished n v0 ... v(n-1)\n"
+                     "       [--search-paths]  cpd-search only: answer through "
+                     "cpd_query_search_paths and\n"
+                     "                  write every route's nodes to <query file>.paths, same "
+                     "format\n");
         return 2;
     }
     // table-search (make_fifos.py:20) or the CPD-heuristic search
@@ -203,7 +212,13 @@ int main(int argc, char** argv) {
     const bool paths = a.has("paths");
     if (paths && search) {
         std::fprintf(stderr, "fifo_auto: --paths needs --alg table-search (the paths of a "
-                             "cpd-search are not extracted)\n");
+                             "cpd-search are extracted with --search-paths)\n");
+        return 2;
+    }
+    const bool search_paths = a.has("search-paths");
+    if (search_paths && !search) {
+        std::fprintf(stderr, "fifo_auto: --search-paths needs --alg cpd-search (the walks of a "
+                             "table-search are extracted with --paths)\n");
         return 2;
     }
     int mcode = cli::method_code(method);
@@ -484,8 +499,15 @@ int main(int argc, char** argv) {
             cpd_query_stats st{};
             cpd_search_stats ss{};
             if (search) {
-                rc = cpd_query_search(ix, &so, &ss);
+                static std::vector<uint64_t> spoff;
+                if (search_paths) {
+                    spoff.resize(nq + 1);
+                    rc = cpd_query_search_paths(ix, &so, 0, spoff.data(), &ss, nullptr);
+                } else {
+                    rc = cpd_query_search(ix, &so, &ss);
+                }
                 if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                if (search_paths) write_paths(ix, qfile, s, t, spoff);
                 if (ss.overflow)
                     std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
                                  (unsigned long long)ss.overflow);

@@ -396,7 +396,8 @@ int  cpd_query_fetch(cpd_index* ix, uint64_t* cost, uint32_t* hops,
  * cpd_query_run does (st, and cpd_query_fetch afterwards returns this walk's
  * cost / hops / finished).  The nodes never depend on the weights
  * (cpd_index_set_weights), only cost does.  This is always the table-search
- * walk: the paths of a preceding cpd_query_search are NOT what it returns.
+ * walk: the paths of a preceding cpd_query_search are NOT what it returns
+ * (cpd_query_search_paths returns those).
  * Known limit, inherited from the walk kernel (cpd_query_run has it too): in
  * a batch large enough for a wave's lanes to be refilled (more than 65536
  * queries on a dense index, 524288 on an RLE one) a refilled lane takes one
@@ -410,8 +411,10 @@ int  cpd_query_fetch(cpd_index* ix, uint64_t* cost, uint32_t* hops,
 int  cpd_query_paths(cpd_index* ix, int32_t k_moves, uint64_t* offsets /* nq+1 */,
                      cpd_query_stats* st);
 /* Path nodes of queries [first, first + count) of the caller's order, back to
- * back: offsets[first+count] - offsets[first] values.  CPD_E_ARG before any
- * cpd_query_paths on the prepared queries, or for a range past nq.           */
+ * back: offsets[first+count] - offsets[first] values — the paths of the last
+ * cpd_query_paths or cpd_query_search_paths on the prepared queries.
+ * CPD_E_ARG before any of the two on the prepared queries, or for a range
+ * past nq.                                                                   */
 int  cpd_query_paths_fetch(cpd_index* ix, uint32_t first, uint32_t count, uint32_t* nodes);
 void cpd_index_free(cpd_index* ix);
 
@@ -494,6 +497,53 @@ int  cpd_query_search(cpd_index* ix, const cpd_search_opts* opts, cpd_search_sta
 /* Per-query counters of the last search: counters[5 q + k] = expanded,
  * inserted, touched, updated, surplus of query q (caller order).            */
 int  cpd_query_search_counters(cpd_index* ix, uint32_t* counters);
+
+/* cpd_query_search with the nodes of every route found.  The incumbent of a
+ * search is "the A* tree from s to the node v* whose expansion last lowered
+ * it, then the row's CPD walk from v* to t"; path q is that route, read when
+ * the search has ended (in whatever pass it ends):
+ *   prefix  the parent chain v* -> par(v*) -> ... -> s, reversed; par(u) is
+ *           the node whose relaxation last set g(u) (the insert or a strictly
+ *           smaller update), so the chain is a tree path;
+ *   suffix  the table-search walk from v* to t, lw(v*) moves, without v*.
+ * finished = 1: prefix nodes + lw(v*) node ids (.xy ids) from s to t, [s]
+ * when s == t; finished = 0 (no incumbent) or 2 (stopped on the workspace):
+ * 0 nodes.  offsets: nq + 1 values in the CALLER's order, offsets[0] = 0;
+ * the nodes stay in HBM for cpd_query_paths_fetch, in the index's path
+ * buffer (as cpd_query_paths: from the arena when one is committed;
+ * CPD_E_OOM naming the bytes when they do not fit), until the next prepare /
+ * run / paths / search_paths call on ix.
+ * The path's cost under the index's current weights is <= the reported cost:
+ * equal, with hops[q] moves, whenever the heuristic is consistent (hscale <=
+ * 1 and every selected weight >= its free-flow weight: nodes are never
+ * re-opened); with hscale > 1 a chain node's g may have improved after the
+ * incumbent was set, and the path returned is that cheaper chain, whose move
+ * count may differ from hops[q] (a search that runs until its stop rule ends
+ * it has expanded every re-opened chain node again: this needs itrs or the
+ * time limit to end it in between).  cost / hops / finished of cpd_query_fetch,
+ * the counters and st stay the oracle's (cpd_query_search's) in every case.
+ * Each search writes its prefix into a pool of prefix_bytes bytes in HBM
+ * (4 per node; info->prefix_nodes nodes over all queries).  0 = automatic:
+ * the smaller of 4 * nq * n bytes (no prefix is longer than n nodes) and
+ * 1/32 of the free HBM, taken before the workspace is sized; the share is
+ * a policy, not a measured optimum.  When the pool is too small the call
+ * returns CPD_E_OOM and the message names the bytes needed (info
+ * ->prefix_nodes * 4): the search's cost / hops / finished / counters are
+ * whole and fetchable, the index and the prepared queries stay usable, and a
+ * second call with at least that many bytes succeeds.  The workspace costs 8
+ * B more per column of capacity (80 / 128 B) than cpd_query_search's.
+ * Does everything cpd_query_search does (st; cpd_query_fetch and
+ * cpd_query_search_counters afterwards).                                     */
+typedef struct cpd_search_paths_info {
+    uint64_t nodes;          /* offsets[nq]                                   */
+    uint64_t prefix_nodes;   /* summed over the queries: what the pool had to hold */
+    uint64_t prefix_bytes;   /* the pool's size used for this call            */
+    double   paths_ms;       /* device time of suffix walk + offsets + join   */
+} cpd_search_paths_info;
+int  cpd_query_search_paths(cpd_index* ix, const cpd_search_opts* opts,
+                            uint64_t prefix_bytes /* 0 = automatic */,
+                            uint64_t* offsets /* nq + 1, caller order */,
+                            cpd_search_stats* st, cpd_search_paths_info* info);
 
 /* ------------------------------------------------------------------------ */
 /* [gpu] Per-kernel device timing (HIP events on the library's stream).      */
