@@ -34,6 +34,7 @@ PART_DIV = 0
 PART_MOD = 1
 INF = 0xFFFFFFFF
 FM_ALL = 0xFFFF
+MAX_WEIGHT_SETS = 8
 
 EXPORTED = [
     "cpd_last_error", "cpd_version", "cpd_partition", "cpd_partition_nbuckets",
@@ -55,6 +56,7 @@ EXPORTED = [
     "cpd_index_append_moves", "cpd_device_arena", "cpd_device_arena_release", "cpd_batch_bytes",
     "cpd_rows_move_bits", "cpd_graph_move_bits", "cpd_bucket_bytes", "cpd_space_check",
     "cpd_query_paths", "cpd_query_paths_fetch", "cpd_query_search_paths",
+    "cpd_index_set_weight_sets", "cpd_query_costs", "cpd_query_costs_fetch",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
@@ -544,6 +546,7 @@ class Index:
                  offsets=None, runs=None, _handle=None):
         self.graph = graph
         self._nq, self._path_offsets = 0, None  # prepared queries; offsets of their paths
+        self._nsets, self._cost_cols = 0, None  # weight sets loaded; columns of the last costs_run
         self._h = C.c_void_p()
         if _handle is not None:
             self._h = _handle
@@ -612,6 +615,7 @@ class Index:
         s, t = _u32(s), _u32(t)
         nq = len(s)
         self._nq, self._path_offsets = 0, None  # cpd_query_batch prepares and runs
+        self._cost_cols = None
         cost = np.empty(nq, np.uint64)
         hops = np.empty(nq, np.uint32)
         fin = np.empty(nq, np.uint8)
@@ -625,6 +629,7 @@ class Index:
     def prepare(self, s, t) -> None:
         s, t = _u32(s), _u32(t)
         self._nq, self._path_offsets = 0, None  # the library drops the last batch's paths
+        self._cost_cols = None                  # ... and its costs
         _check(lib.cpd_query_prepare(self._h, _ptr(s, u32p), _ptr(t, u32p), C.c_uint32(len(s))))
         self._nq = len(s)
 
@@ -676,6 +681,54 @@ class Index:
         _check(lib.cpd_query_paths_fetch(self._h, C.c_uint32(first), C.c_uint32(count),
                                          _ptr(nodes, u32p)))
         return nodes
+
+    def set_weight_sets(self, sets=None) -> None:
+        """Weight sets for costs() (cpd_index_set_weight_sets): a list of up to
+        MAX_WEIGHT_SETS arrays of m weights in original edge order, None in
+        the list = the free-flow weights; None or an empty list clears them.
+        Independent of set_weights()."""
+        sets = [] if sets is None else list(sets)
+        arrs = [None if w is None else _u32(w) for w in sets]
+        ptrs = (u32p * max(1, len(arrs)))(*[_ptr(a, u32p) for a in arrs])
+        _check(lib.cpd_index_set_weight_sets(self._h, C.c_uint32(len(arrs)),
+                                             ptrs if arrs else None))
+        self._nsets = len(arrs)
+
+    def costs(self, s, t, k_moves: int = -1, slice_moves: int = 0):
+        """The table-search walks of (s, t) costed under the loaded weight sets
+        in one walk (cpd_query_costs): (costs u64[nq, C], hops, finished,
+        stats).  slice_moves = 0: C = the number of sets, column j the cost
+        under set j; slice_moves = S > 0: C = 1, move h of a walk costed under
+        set min(h // S, nsets - 1)."""
+        self.prepare(s, t)
+        st = self.costs_run(k_moves, slice_moves)
+        costs, hops, fin = self.costs_fetch()
+        return costs, hops, fin, st
+
+    def costs_run(self, k_moves: int = -1, slice_moves: int = 0) -> dict:
+        """cpd_query_costs on the prepared queries: stats."""
+        self._cost_cols = None
+        st = QueryStats()
+        _check(lib.cpd_query_costs(self._h, C.c_int32(k_moves), C.c_uint32(slice_moves),
+                                   C.byref(st)))
+        self._cost_cols = 1 if slice_moves else self._nsets
+        return {k: getattr(st, k) for k, _ in QueryStats._fields_}
+
+    def costs_fetch(self):
+        """(costs u64[nq, C], hops, finished) of the last costs_run()
+        (cpd_query_costs_fetch).  The library copies nq * C values, so this
+        refuses (CPD_E_ARG, as the library would) when the C of that very call
+        is not at hand."""
+        if self._cost_cols is None:
+            raise CpdError(CPD_E_ARG, "costs fetch: no costs() / costs_run() on the prepared "
+                                      "queries yet")
+        nq = self._nq
+        costs = np.empty((nq, self._cost_cols), np.uint64)
+        hops = np.empty(nq, np.uint32)
+        fin = np.empty(nq, np.uint8)
+        _check(lib.cpd_query_costs_fetch(self._h, _ptr(costs, u64p), _ptr(hops, u32p),
+                                         _ptr(fin, u8p)))
+        return costs, hops, fin
 
     def search(self, s, t, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
                capacity=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,

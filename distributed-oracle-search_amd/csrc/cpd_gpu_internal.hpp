@@ -486,6 +486,22 @@ struct cpd_index {
     std::vector<uint64_t> poff_h;
     DevBuf<uint32_t> pnodes;
     bool paths_ready = false;
+    // costs under several weight sets (cpd_index_set_weight_sets /
+    // cpd_query_costs): the set table — a record of wset_words (4 or 8) u32
+    // per adjacency slot, word j = the slot's weight in set j — and the
+    // result buffers of the last cpd_query_costs in sorted order (cs_cols
+    // values per query: nsets, or 1 when sliced); costs_ready: they are those
+    // of the prepared queries.  Independent of adj_sel / custom_w.  Carved
+    // from the arena when one is committed, like every DevBuf allocated
+    // inside an ArenaScope: the arena never takes them back, so a larger
+    // table or batch than any before uses up that many more arena bytes.
+    DevBuf<uint32_t> wsets;
+    uint32_t nsets = 0, wset_words = 0;
+    DevBuf<uint64_t> cs_cost;
+    DevBuf<uint32_t> cs_hops;
+    DevBuf<uint8_t> cs_fin;
+    uint32_t cs_cols = 0;
+    bool costs_ready = false;
     // search paths (cpd_query_search_paths), scratch of one call, freed when
     // it returns (the cursor stays): the prefix pool and its cursor;
     // per query (sorted order) the prefix's place and length, v* and lw(v*);

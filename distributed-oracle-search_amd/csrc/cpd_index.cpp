@@ -450,6 +450,7 @@ int cpd_query_prepare(cpd_index* ix, const uint32_t* s, const uint32_t* t, uint3
         ix->nq = 0;
         ix->searched = false;
         ix->paths_ready = false;
+        ix->costs_ready = false;
         const size_t m = std::max<uint32_t>(nq, 1u);
         for (DevBuf<uint32_t>* b : {&ix->qin_s, &ix->qin_t, &ix->qkey, &ix->qkey2, &ix->qval,
                                     &ix->qperm, &ix->qs, &ix->qt, &ix->qrow, &ix->hops})
@@ -493,6 +494,23 @@ int cpd_query_prepare(cpd_index* ix, const uint32_t* s, const uint32_t* t, uint3
 
 namespace {
 
+// Algorithmic bytes of a table-search walk of nq queries and `moves` moves.
+double walk_model_bytes(const cpd_index* ix, bool dense, uint32_t nq, uint64_t moves) {
+    // dense: per query 8 (s,t) + 13 (outputs) + 4 (row); per move one 4-B
+    // move word + one 8-B packed edge
+    if (dense) return 25.0 * nq + 12.0 * (double)moves;
+    // SURVEY.md §8(d) B_q = 8 + 12 + 8 + L * (4 ceil(log2 R) + 16)
+    double mean_log = 0.0;
+    if (ix->nrows) {
+        double s = 0.0;
+        for (uint32_t i = 0; i < ix->nrows; ++i)
+            s += std::ceil(std::log2((double)std::max<uint64_t>(
+                2, ix->offsets[i + 1] - ix->offsets[i])));
+        mean_log = s / ix->nrows;
+    }
+    return 28.0 * nq + (double)moves * (4.0 * mean_log + 16.0);
+}
+
 // The table-search walk of the prepared queries (cpd_query_run; the count
 // pass of cpd_query_paths): cost / hops / fin in sorted order, sums in agg.
 // Returns the launch's algorithmic bytes when timing is on (else 0).
@@ -528,22 +546,7 @@ double run_walk(cpd_index* ix, int32_t k_moves, cpd_query_stats* st) {
         Agg& ag = g->agg[dense ? "table_search_dense" : "table_search"];
         ag.launches++;
         ag.ms += ms;
-        if (dense) {
-            // per query 8 (s,t) + 13 (outputs) + 4 (row); per move one
-            // 4-B move word + one 8-B packed edge
-            bytes = 25.0 * nq + 12.0 * (double)hagg[1];
-        } else {
-            // SURVEY.md §8(d) B_q = 8 + 12 + 8 + L * (4 ceil(log2 R) + 16)
-            double mean_log = 0.0;
-            if (ix->nrows) {
-                double s = 0.0;
-                for (uint32_t i = 0; i < ix->nrows; ++i)
-                    s += std::ceil(std::log2((double)std::max<uint64_t>(
-                        2, ix->offsets[i + 1] - ix->offsets[i])));
-                mean_log = s / ix->nrows;
-            }
-            bytes = 28.0 * nq + (double)hagg[1] * (4.0 * mean_log + 16.0);
-        }
+        bytes = walk_model_bytes(ix, dense, nq, hagg[1]);
         ag.bytes += bytes;
     }
     if (st) {
@@ -708,6 +711,148 @@ int cpd_query_paths_fetch(cpd_index* ix, uint32_t first, uint32_t count, uint32_
         HIP_CHECK(hipMemcpyAsync(nodes, ix->pnodes.p + a, (size_t)(b - a) * sizeof(uint32_t),
                                  hipMemcpyDeviceToHost, g->stream));
         HIP_CHECK(hipStreamSynchronize(g->stream));
+    });
+}
+
+int cpd_index_set_weight_sets(cpd_index* ix, uint32_t nsets, const uint32_t* const* w) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        CPD_REQUIRE(nsets <= CPD_MAX_WEIGHT_SETS, CPD_E_ARG,
+                    "weight sets: " + std::to_string(nsets) + " sets, at most " +
+                        std::to_string(CPD_MAX_WEIGHT_SETS));
+        CPD_REQUIRE(nsets == 0 || w, CPD_E_ARG, "weight sets: null argument");
+        cpd_graph* g = ix->g;
+        g->select();
+        if (!nsets) {
+            ix->wsets.release();
+            ix->nsets = ix->wset_words = 0;
+            return;
+        }
+        // one record per adjacency slot, as packed_adjacency lays the slots
+        // out: word j = the slot's weight in set j, zeros past nsets and
+        // past the out-degree; one more record of zeros closes the table
+        // (what a lane that takes no move loads)
+        const uint32_t kw = weight_set_words(nsets);
+        const size_t stride = (size_t)1 << g->adj_shift;
+        // the kernel takes the zero record's index as u32
+        CPD_REQUIRE(stride * g->n < (1ull << 32), CPD_E_RANGE,
+                    "weight sets: more than 2^32 adjacency slots");
+        std::vector<uint32_t> tab((stride * g->n + 1u) * kw, 0u);
+        for (uint32_t j = 0; j < nsets; ++j) {
+            const uint32_t* wj = w[j];  // NULL: free flow
+            for (uint32_t c = 0; c < g->n; ++c)
+                for (uint32_t e = g->rowc_host[c]; e < g->rowc_host[c + 1]; ++e)
+                    tab[((size_t)c * stride + (e - g->rowc_host[c])) * kw + j] =
+                        wj ? wj[g->edge_perm[e]] : g->w_free_col[e];
+        }
+        ix->nsets = ix->wset_words = 0;  // none loaded should the upload fail
+        {
+            ArenaScope carve;
+            ix->wsets.upload(tab.data(), tab.size(), g->stream);
+        }
+        HIP_CHECK(hipStreamSynchronize(g->stream));
+        ix->nsets = nsets;
+        ix->wset_words = kw;
+    });
+}
+
+int cpd_query_costs(cpd_index* ix, int32_t k_moves, uint32_t slice_moves, cpd_query_stats* st) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        CPD_REQUIRE(ix->nsets, CPD_E_ARG, "costs: no weight sets loaded (cpd_index_set_weight_sets)");
+        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
+                    "costs: index incomplete (" + std::to_string(ix->added) + " of " +
+                        std::to_string(ix->nrows) + " rows appended)");
+        cpd_graph* g = ix->g;
+        g->select();
+        hipStream_t s = g->stream;
+        const uint32_t nq = ix->nq;
+        const uint32_t cols = slice_moves ? 1u : ix->nsets;
+        ix->costs_ready = false;
+        const bool dense = ix->use_dense();
+        if (dense && !ix->dense_ready) ensure_dense(ix);
+        {
+            ArenaScope carve;
+            const size_t m = std::max<uint32_t>(nq, 1u);
+            ix->cs_cost.alloc(m * cols);
+            ix->cs_hops.alloc(m);
+            ix->cs_fin.alloc(m);
+        }
+        HIP_CHECK(hipMemsetAsync(ix->agg.p, 0, 3 * sizeof(unsigned long long), s));
+        Events<2> ev(g);
+        const hipEvent_t a = ev.e[0], b = ev.e[1];
+        HIP_CHECK(hipEventRecord(a, s));
+        (void)hipGetLastError();
+        // the route needs the adjacency's heads only: the free-flow one serves
+        if (nq && dense)
+            launch_table_costs_dense(g->adj.p, g->adj_shift, ix->dense.p, g->npad, g->tlb,
+                                     ix->wsets.p, ix->nsets, slice_moves, ix->qs.p, ix->qt.p,
+                                     ix->qrow.p, nq, k_moves, g->n, ix->cs_cost.p, ix->cs_hops.p,
+                                     ix->cs_fin.p, ix->agg.p, s);
+        else if (nq)
+            launch_table_costs(g->adj.p, g->adj_shift, ix->off.p, ix->runs.p, ix->wsets.p,
+                               ix->nsets, slice_moves, ix->qs.p, ix->qt.p, ix->qrow.p, nq, k_moves,
+                               g->n, ix->cs_cost.p, ix->cs_hops.p, ix->cs_fin.p, ix->agg.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(b, s));
+        unsigned long long hagg[3] = {0, 0, 0};  // finished, moves, cost (wave_stats)
+        HIP_CHECK(hipMemcpyAsync(hagg, ix->agg.p, sizeof hagg, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+        if (g->timing) {
+            // the walk's bytes + a record (sliced: one word) per move + the
+            // stored columns
+            Agg& ag = g->agg[dense ? "table_costs_dense" : "table_costs"];
+            ag.launches++;
+            ag.ms += ms;
+            ag.bytes += walk_model_bytes(ix, dense, nq, hagg[1]) +
+                        (slice_moves ? 4.0 : 4.0 * ix->wset_words) * (double)hagg[1] +
+                        8.0 * cols * nq;
+        }
+        if (st) {
+            st->queries = nq;
+            st->finished = hagg[0];
+            st->hops = hagg[1];
+            st->cost = hagg[2];
+            st->kernel_ms = ms;
+        }
+        ix->cs_cols = cols;
+        ix->costs_ready = true;
+    });
+}
+
+int cpd_query_costs_fetch(cpd_index* ix, uint64_t* costs, uint32_t* hops, uint8_t* finished) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        CPD_REQUIRE(ix->costs_ready, CPD_E_ARG,
+                    "costs fetch: no cpd_query_costs on the prepared queries yet");
+        cpd_graph* g = ix->g;
+        g->select();
+        const uint32_t nq = ix->nq, cols = ix->cs_cols;
+        if (!nq) return;
+        // sorted order -> the caller's, on the GPU, then copied out
+        hipStream_t st = g->stream;
+        ix->qout.alloc((size_t)nq * 8u * cols);
+        if (costs) {
+            launch_scatter_u64_rows(ix->cs_cost.p, ix->qperm.p, nq, cols,
+                                    reinterpret_cast<uint64_t*>(ix->qout.p), st);
+            HIP_CHECK(hipMemcpyAsync(costs, ix->qout.p, (size_t)nq * 8u * cols,
+                                     hipMemcpyDeviceToHost, st));
+        }
+        if (hops) {
+            HIP_CHECK(hipStreamSynchronize(st));  // qout is reused
+            launch_scatter_u32(ix->cs_hops.p, ix->qperm.p, nq, 1u,
+                               reinterpret_cast<uint32_t*>(ix->qout.p), st);
+            HIP_CHECK(hipMemcpyAsync(hops, ix->qout.p, nq * 4ull, hipMemcpyDeviceToHost, st));
+        }
+        if (finished) {
+            HIP_CHECK(hipStreamSynchronize(st));
+            launch_scatter_u8(ix->cs_fin.p, ix->qperm.p, nq, ix->qout.p, st);
+            HIP_CHECK(hipMemcpyAsync(finished, ix->qout.p, nq, hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
     });
 }
 

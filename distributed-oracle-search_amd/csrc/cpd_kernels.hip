@@ -3145,6 +3145,224 @@ __global__ __launch_bounds__(256) void table_walk_paths(
     }
 }
 
+// Costs under several weight sets (cpd_query_costs): table_walk's walk once,
+// summing the weight of every edge taken under up to KW weight sets.  The
+// frame (a wave owns a chunk, lanes are refilled), the retire condition and
+// walk_begin / walk_move are table_walk's, so hops, finished and the route
+// are the plain walk's; only what is summed differs.
+// wsets holds one record of KW u32 per adjacency slot — record (col << SHIFT)
+// + slot, word j = the slot's weight in set j, 0 for j >= nsets and for slots
+// past the out-degree — and one all-zero record after the last slot (record
+// zrec), so a hop reads its edge's weight in every set with KW / 4 16-B
+// loads.  slice == 0: KW running u64 sums per lane, the first nsets of them
+// stored (costs_out[q * nsets + j]).  slice == S > 0 (a wave-uniform
+// branch, taken once: each mode has its own loop, so that the sliced one
+// carries one sum and neither carries the other's registers): one sum; move
+// h of a walk adds word min(h / S, nsets - 1) of its record — kept per lane
+// as a set index and a countdown, no division — and one value is stored
+// (costs_out[q]).
+// The record's address needs the move, but nothing the NEXT hop needs depends
+// on the record: it is loaded when the move is known (into pend) and added
+// one iteration later, after that iteration's own loads (move word or first
+// run probe, the co-fetched adjacency row) are issued.  Loads return in
+// order, so the wait for the record leaves the newer loads in flight and its
+// round trip overlaps theirs.  For the compiler to keep it so, pend has ONE
+// definition in the loop — the load, which every lane issues: a lane that
+// takes no move (idle, arrived, stopped) loads the zero record — and ONE
+// place where every lane adds it, fenced behind the hop's loads and pinned
+// (an empty asm that takes the sums) before the next record's loads, so that
+// the record's registers are free for them: left alone, hipcc sinks the adds
+// below those loads, keeps two copies of the record and waits for the new
+// one at the loop's end.
+// What this achieves, read off the ISA: in the SLICED loop the record's one
+// dword is waited for behind the next hop's loads (s_waitcnt vmcnt(5), the
+// add, no wait after the record's load).  In the ALL-SETS loop it does NOT:
+// hipcc copies words of the record's 16-B register tuples out right after
+// the loads, behind s_waitcnt vmcnt(1) / vmcnt(0) at KW 8 and vmcnt(0) at KW
+// 4 — the whole record is waited for where it is loaded, at both widths, and
+// the add a hop later needs no wait.  Loading the record as KW dwords (their
+// indices hidden from the load vectorizer, which otherwise merges them back)
+// does take it off the chain — counted waits vmcnt(12) .. vmcnt(5) before the
+// adds, none after the loads — and was measured (profiles/costs/
+// costs_ab_word_loads.jsonl): no faster on dense rows, 2% slower on RLE rows
+// and, at 72 VGPRs and 7 waves per SIMD, 33% slower on RLE rows at KW 8.  So
+// the 16-B loads stay; the all-sets loop keeps the shape above because it is
+// the sliced loop's code (one function, SLICED a template flag) and costs it
+// nothing.  A lane that retires adds its last record before it
+// stores (the only other wait for it, taken only when some lane retires) and
+// restarts its sums at minus that record, which the common add then brings
+// to 0 (u64 arithmetic wraps).  walk_begin's loads are waited for where they
+// are issued (settle): one left pending at the loop's head would make the
+// retire test's wait cover the record as well.
+template <int SHIFT, int KW, bool SLICED, class Rows>
+__device__ __forceinline__ void costs_walk(
+    const uint2* __restrict__ adj, Rows rows, const uint32_t* __restrict__ wsets, uint32_t zrec,
+    const uint32_t* __restrict__ qs, const uint32_t* __restrict__ qt,
+    const uint32_t* __restrict__ qrow, uint32_t nq, uint32_t chunk, uint32_t limit,
+    uint32_t nsets, uint32_t slice, uint64_t* __restrict__ costs_out,
+    uint32_t* __restrict__ hops_out, uint8_t* __restrict__ fin_out,
+    unsigned long long* __restrict__ agg) {
+    static_assert(KW == 4 || KW == 8, "records are one or two 16-B loads");
+    constexpr bool kDense = std::is_same<Rows, DenseRows>::value;
+    constexpr int NQ = SHIFT == 2 ? 2 : 1;  // 16-B pieces of an adjacency row
+    constexpr int NS = SLICED ? 1 : KW;     // sums per lane
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t q0l = wave * chunk;
+    const uint32_t q0 = q0l < nq ? (uint32_t)q0l : nq;
+    const uint32_t q1 = (uint32_t)min((uint64_t)nq, q0l + chunk);
+    const uint32_t ncol = SLICED ? 1u : nsets;  // values stored per query
+    uint64_t sum_cost = 0;
+    uint32_t sum_hops = 0, sum_fin = 0;
+    // the sums so far, the pending record excluded, as 32-bit halves: the add
+    // is then an add and an add-with-carry that read the record's register
+    // itself (a 64-bit add wants the record widened into a register pair, a
+    // copy that waits for the record's load where it is made)
+    uint32_t alo[NS], ahi[NS];
+    uint32_t pend[NS];   // the record of the last iteration (sliced: its one word)
+    uint32_t set = 0, left = slice;  // sliced: the set of the next move, moves left in it
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        alo[j] = ahi[j] = 0;
+        pend[j] = 0;
+    }
+    WalkState w;
+    uint32_t next = q0;  // wave-uniform: first query of the chunk not yet started
+    w.q = kIdleQ;        // idle: column 0 of row 0 stays loadable
+    w.cur = 0;
+    w.t = 0;
+    w.hops = 0;
+    w.bad = false;
+    w.cost = 0;
+    w.pos = 0;
+    w.R = 0;
+    w.row = rows_base(rows);
+    auto settle = [&]() {  // the walk's state is in registers, no load of it pending
+        if constexpr (kDense) asm volatile("" ::"v"(w.cur), "v"(w.t), "v"(w.row));
+        else asm volatile("" ::"v"(w.cur), "v"(w.t), "v"(w.row), "v"(w.R));
+    };
+    if (next + lane < q1) walk_begin(w, next + lane, qs, qt, qrow, rows);
+    settle();
+    next = min(q1, next + 64u);
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    for (;;) {
+        // retire finished walks; their lanes take the next queries of the chunk
+        const bool idle = w.q == kIdleQ;
+        const bool done = !idle && (w.cur == w.t || w.hops >= limit || w.bad);
+        const uint64_t m = __ballot(done);
+        if (m) {
+            if (done) {
+                const uint32_t fin = w.cur == w.t ? 1u : 0u;
+                uint64_t* __restrict__ o = costs_out + (size_t)w.q * ncol;
+#pragma unroll
+                for (int j = 0; j < NS; ++j) {
+                    const uint64_t v = (((uint64_t)ahi[j] << 32) | alo[j]) + pend[j];
+                    if ((uint32_t)j < ncol) o[j] = v;
+                    if (j == 0) sum_cost += v;
+                    alo[j] = 0u - pend[j];  // minus the record: + pend below gives 0
+                    ahi[j] = pend[j] ? 0xFFFFFFFFu : 0u;
+                }
+                hops_out[w.q] = w.hops;
+                fin_out[w.q] = (uint8_t)fin;
+                sum_hops += w.hops;
+                sum_fin += fin;
+                set = 0;
+                left = slice;
+                const uint32_t nqi = next + (uint32_t)__builtin_popcountll(m & lt_mask);
+                if (nqi < q1) walk_begin(w, nqi, qs, qt, qrow, rows);
+                else w.q = kIdleQ;
+                settle();
+            }
+            next = min(q1, next + (uint32_t)__builtin_popcountll(m));
+        }
+        if (!__any(w.q != kIdleQ)) break;
+        // this hop's loads that depend on cur alone, for every lane (an idle
+        // or arrived lane stands on a valid column of a valid row)
+        uint4 p[NQ];
+        uint32_t word;
+        if (SHIFT == 0) {
+            const uint2 e = adj[w.cur];
+            p[0] = make_uint4(e.x, e.y, kNoEdge, 0u);
+        } else if (SHIFT <= 2) {
+            const uint4* a4 = reinterpret_cast<const uint4*>(adj) + (size_t)w.cur * NQ;
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) p[k] = a4[k];
+        }
+        if constexpr (kDense) word = w.row[w.cur >> (5u - rows.tb.lb)];
+        else word = w.row[w.pos];  // the run search's first probe
+        // the last iteration's record, behind them
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const uint32_t lo = alo[j] + pend[j];
+            ahi[j] += lo < pend[j] ? 1u : 0u;
+            alo[j] = lo;
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j) asm volatile("" : "+v"(alo[j]), "+v"(ahi[j]));
+        __builtin_amdgcn_sched_barrier(0);
+        const bool walking = w.q != kIdleQ && w.cur != w.t;
+        uint32_t mv;
+        if constexpr (kDense) {
+            const uint32_t cm = 31u >> rows.tb.lb, mm = (1u << (1u << rows.tb.lb)) - 1u;
+            mv = (word >> ((w.cur & cm) << rows.tb.lb)) & mm;
+        } else {
+            mv = word & 0xFu;
+            if (walking) mv = walk_move(w, rows);
+        }
+        const bool slot_ok = (mv >> SHIFT) == 0u;  // else: names no slot of cur, malformed row
+        const uint32_t slot = mv & ((1u << SHIFT) - 1u);
+        uint32_t ex;
+        if (SHIFT <= 2) {
+            const uint4 e = (NQ == 2 && (slot & 2u)) ? p[NQ - 1] : p[0];
+            ex = (slot & 1u) ? e.z : e.x;
+        } else {
+            ex = adj[((size_t)w.cur << SHIFT) + slot].x;
+        }
+        const bool step = walking && slot_ok && ex != kNoEdge;
+        w.bad = w.bad || (walking && !step);
+        const size_t rec = step ? ((size_t)w.cur << SHIFT) + slot : (size_t)zrec;
+        if constexpr (SLICED) {
+            pend[0] = wsets[rec * KW + set];
+            if (step && --left == 0u) {
+                left = slice;
+                if (set + 1u < nsets) ++set;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < KW / 4; ++k) {  // see "waited for where it is loaded" above
+                const uint4 r = reinterpret_cast<const uint4*>(wsets)[rec * (KW / 4) + k];
+                pend[4 * k] = r.x;
+                pend[4 * k + 1] = r.y;
+                pend[4 * k + 2] = r.z;
+                pend[4 * k + 3] = r.w;
+            }
+        }
+        if (step) {
+            w.cur = ex;
+            ++w.hops;
+        }
+    }
+    wave_stats(sum_cost, sum_hops, sum_fin, agg);
+}
+
+template <int SHIFT, int KW, class Rows>
+__global__ __launch_bounds__(256) void table_walk_costs(
+    const uint2* __restrict__ adj, Rows rows, const uint32_t* __restrict__ wsets, uint32_t zrec,
+    const uint32_t* __restrict__ qs, const uint32_t* __restrict__ qt,
+    const uint32_t* __restrict__ qrow, uint32_t nq, uint32_t chunk, uint32_t limit,
+    uint32_t nsets, uint32_t slice, uint64_t* __restrict__ costs_out,
+    uint32_t* __restrict__ hops_out, uint8_t* __restrict__ fin_out,
+    unsigned long long* __restrict__ agg) {
+    // the mode is the launch's (wave-uniform): one branch, each side its own loop
+    if (slice)
+        costs_walk<SHIFT, KW, true>(adj, rows, wsets, zrec, qs, qt, qrow, nq, chunk, limit, nsets,
+                                    slice, costs_out, hops_out, fin_out, agg);
+    else
+        costs_walk<SHIFT, KW, false>(adj, rows, wsets, zrec, qs, qt, qrow, nq, chunk, limit, nsets,
+                                     slice, costs_out, hops_out, fin_out, agg);
+}
+
 __device__ void wave_stats(uint64_t cost, uint32_t hops, uint32_t fin,
                            unsigned long long* __restrict__ agg) {
     // wave reduction, one atomic per wave per counter
@@ -4652,18 +4870,30 @@ void launch_expand_rows(const uint64_t* offsets, const uint32_t* runs, const uin
 // ran out of workgroup slots: 8.2M against 11.4M; profiles/walk_wpb_ab/).
 constexpr uint32_t kDenseWaves = 1024, kDenseWpb = 1, kRleWaves = 8192, kRleWpb = 4;
 
-template <class Rows>
-static void launch_walk(const uint2* adj, uint32_t shift, const Rows& rows, const uint32_t* qs,
-                        const uint32_t* qt, const uint32_t* qrow, uint32_t nq, uint32_t limit,
-                        uint64_t* cost, uint32_t* hops, uint8_t* fin, unsigned long long* agg,
-                        uint32_t waves_target, uint32_t chunk_max, hipStream_t s, uint32_t wpb) {
+// The launch shape of the three walks (table_walk, table_walk_paths,
+// table_walk_costs): queries per wave and the grid for them.
+struct WalkShape {
+    uint32_t chunk;
+    dim3 grid, blk;
+};
+static WalkShape walk_shape(uint32_t nq, uint32_t waves_target, uint32_t chunk_max, uint32_t wpb) {
     constexpr uint32_t unit = 64u;
     uint64_t chunk = ((uint64_t)nq + waves_target - 1u) / waves_target;
     chunk = std::min<uint64_t>(chunk, std::max(unit, chunk_max));
     chunk = std::max<uint64_t>(unit, (chunk + unit - 1u) / unit * unit);
     const uint64_t waves = ((uint64_t)nq + chunk - 1u) / chunk;
-    const dim3 grid((uint32_t)std::max<uint64_t>(1u, (waves + wpb - 1u) / wpb)), blk(64u * wpb);
-    const uint32_t c = (uint32_t)chunk;
+    return {(uint32_t)chunk, dim3((uint32_t)std::max<uint64_t>(1u, (waves + wpb - 1u) / wpb)),
+            dim3(64u * wpb)};
+}
+
+template <class Rows>
+static void launch_walk(const uint2* adj, uint32_t shift, const Rows& rows, const uint32_t* qs,
+                        const uint32_t* qt, const uint32_t* qrow, uint32_t nq, uint32_t limit,
+                        uint64_t* cost, uint32_t* hops, uint8_t* fin, unsigned long long* agg,
+                        uint32_t waves_target, uint32_t chunk_max, hipStream_t s, uint32_t wpb) {
+    const WalkShape sh = walk_shape(nq, waves_target, chunk_max, wpb);
+    const dim3 grid = sh.grid, blk = sh.blk;
+    const uint32_t c = sh.chunk;
 #define CPD_WALK(SH, IL)                                                                       \
     launch(kern::table_walk<SH, IL, Rows>, grid, blk, s, adj, rows, qs, qt, qrow, nq, c, limit, \
            cost, hops, fin, agg)
@@ -4710,13 +4940,9 @@ static void launch_walk_paths(const uint2* adj, uint32_t shift, const Rows& rows
                               const uint32_t* node_of_col, uint32_t nq, uint32_t limit,
                               uint32_t* nodes, uint32_t waves_target, uint32_t chunk_max,
                               hipStream_t s, uint32_t wpb) {
-    constexpr uint32_t unit = 64u;
-    uint64_t chunk = ((uint64_t)nq + waves_target - 1u) / waves_target;
-    chunk = std::min<uint64_t>(chunk, std::max(unit, chunk_max));
-    chunk = std::max<uint64_t>(unit, (chunk + unit - 1u) / unit * unit);
-    const uint64_t waves = ((uint64_t)nq + chunk - 1u) / chunk;
-    const dim3 grid((uint32_t)std::max<uint64_t>(1u, (waves + wpb - 1u) / wpb)), blk(64u * wpb);
-    const uint32_t c = (uint32_t)chunk;
+    const WalkShape sh = walk_shape(nq, waves_target, chunk_max, wpb);
+    const dim3 grid = sh.grid, blk = sh.blk;
+    const uint32_t c = sh.chunk;
     const size_t shm = (size_t)wpb * kern::kPathStage * 64u * sizeof(uint32_t);
 #define CPD_WALK_PATHS(SH)                                                                    \
     launch_shm(kern::table_walk_paths<SH, Rows>, grid, blk, shm, s, adj, rows, qs, qt, qrow, qperm, \
@@ -4750,6 +4976,64 @@ void launch_table_paths(const uint32_t* adj, uint32_t shift, const uint64_t* off
     launch_walk_paths(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs}, qs,
                       qt, qrow, qperm, poff, node_of_col, nq, walk_limit(kmoves, n), nodes,
                       kRleWaves, 1u << 30, s, kRleWpb);
+}
+
+// Costs under several weight sets: launch_walk's chunking with the walk's own
+// constants (kDenseWaves / kDenseWpb, kRleWaves / kRleWpb); records of 4
+// words for up to 4 sets, of 8 above.
+uint32_t weight_set_words(uint32_t nsets) { return nsets <= 4u ? 4u : 8u; }
+
+template <class Rows>
+static void launch_walk_costs(const uint2* adj, uint32_t shift, const Rows& rows,
+                              const uint32_t* wsets, uint32_t nsets, uint32_t slice,
+                              const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
+                              uint32_t nq, uint32_t n, uint32_t limit, uint64_t* costs,
+                              uint32_t* hops, uint8_t* fin, unsigned long long* agg, uint32_t waves_target,
+                              uint32_t chunk_max, hipStream_t s, uint32_t wpb) {
+    const WalkShape sh = walk_shape(nq, waves_target, chunk_max, wpb);
+    const dim3 grid = sh.grid, blk = sh.blk;
+    const uint32_t c = sh.chunk;
+    const bool wide = weight_set_words(nsets) == 8u;
+    const uint32_t zrec = n << shift;  // the zero record after the last slot
+#define CPD_WALK_COSTS(SH)                                                                      \
+    do {                                                                                        \
+        if (wide)                                                                               \
+            launch(kern::table_walk_costs<SH, 8, Rows>, grid, blk, s, adj, rows, wsets, zrec, qs, \
+                   qt, qrow, nq, c, limit, nsets, slice, costs, hops, fin, agg);                \
+        else                                                                                    \
+            launch(kern::table_walk_costs<SH, 4, Rows>, grid, blk, s, adj, rows, wsets, zrec, qs, \
+                   qt, qrow, nq, c, limit, nsets, slice, costs, hops, fin, agg);                \
+    } while (0)
+    switch (shift) {
+        case 0: CPD_WALK_COSTS(0); break;
+        case 1: CPD_WALK_COSTS(1); break;
+        case 2: CPD_WALK_COSTS(2); break;
+        case 3: CPD_WALK_COSTS(3); break;
+        default: CPD_WALK_COSTS(4); break;
+    }
+#undef CPD_WALK_COSTS
+}
+
+void launch_table_costs_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                              uint32_t npad, uint32_t lb, const uint32_t* wsets, uint32_t nsets,
+                              uint32_t slice, const uint32_t* qs, const uint32_t* qt,
+                              const uint32_t* qrow, uint32_t nq, int32_t kmoves, uint32_t n,
+                              uint64_t* costs, uint32_t* hops, uint8_t* fin,
+                              unsigned long long* agg, hipStream_t s) {
+    const kern::DenseRows rows{dense, npad >> (5u - lb), kern::Tbl{lb}};
+    launch_walk_costs(reinterpret_cast<const uint2*>(adj), shift, rows, wsets, nsets, slice, qs, qt,
+                      qrow, nq, n, walk_limit(kmoves, n), costs, hops, fin, agg, kDenseWaves, 1024u, s,
+                      kDenseWpb);
+}
+
+void launch_table_costs(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                        const uint32_t* runs, const uint32_t* wsets, uint32_t nsets, uint32_t slice,
+                        const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow, uint32_t nq,
+                        int32_t kmoves, uint32_t n, uint64_t* costs, uint32_t* hops, uint8_t* fin,
+                        unsigned long long* agg, hipStream_t s) {
+    launch_walk_costs(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs},
+                      wsets, nsets, slice, qs, qt, qrow, nq, n, walk_limit(kmoves, n), costs, hops,
+                      fin, agg, kRleWaves, 1u << 30, s, kRleWpb);
 }
 
 // Path offsets: lens[q] = hops[q] + 1 (caller order), lens[nq] = 0, then an
@@ -4924,6 +5208,10 @@ static void scatter_t(const T* in, const uint32_t* perm, uint32_t nq, uint32_t k
 void launch_scatter_u64(const uint64_t* in, const uint32_t* perm, uint32_t nq, uint64_t* out,
                         hipStream_t st) {
     scatter_t(in, perm, nq, 1u, out, st);
+}
+void launch_scatter_u64_rows(const uint64_t* in, const uint32_t* perm, uint32_t nq, uint32_t k,
+                             uint64_t* out, hipStream_t st) {
+    scatter_t(in, perm, nq, k, out, st);
 }
 void launch_scatter_u32(const uint32_t* in, const uint32_t* perm, uint32_t nq, uint32_t k,
                         uint32_t* out, hipStream_t st) {

@@ -263,6 +263,31 @@ void launch_table_paths(const uint32_t* adj, uint32_t shift, const uint64_t* off
                         const uint32_t* node_of_col, uint32_t nq, int32_t kmoves, uint32_t n,
                         uint32_t* nodes, hipStream_t s);
 
+// Costs under several weight sets (cpd_query_costs): the table-search walk
+// once, summing every edge taken under nsets (1..8) weight sets.  wsets: one
+// record of weight_set_words(nsets) (4 or 8) u32 per adjacency slot, record
+// (column << shift) + slot, word j = the slot's weight in set j (0 for j >=
+// nsets and for slots past the out-degree), and one record of zeros after
+// the last slot (record n << shift).  slice == 0: costs[q * nsets + j];
+// slice == S > 0: costs[q], move h costed under set min(h / S, nsets - 1).
+// costs / hops / fin in the sorted order of qs; agg as the walk's, cost = the
+// sum of column 0.
+uint32_t weight_set_words(uint32_t nsets);
+void launch_table_costs_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                              uint32_t npad, uint32_t lb, const uint32_t* wsets, uint32_t nsets,
+                              uint32_t slice, const uint32_t* qs, const uint32_t* qt,
+                              const uint32_t* qrow, uint32_t nq, int32_t kmoves, uint32_t n,
+                              uint64_t* costs, uint32_t* hops, uint8_t* fin,
+                              unsigned long long* agg, hipStream_t s);
+void launch_table_costs(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                        const uint32_t* runs, const uint32_t* wsets, uint32_t nsets, uint32_t slice,
+                        const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow, uint32_t nq,
+                        int32_t kmoves, uint32_t n, uint64_t* costs, uint32_t* hops, uint8_t* fin,
+                        unsigned long long* agg, hipStream_t s);
+// out[perm[i] * k + j] = in[i * k + j] (k u64 per query, to the caller's order)
+void launch_scatter_u64_rows(const uint64_t* in, const uint32_t* perm, uint32_t nq, uint32_t k,
+                             uint64_t* out, hipStream_t st);
+
 // CPD-heuristic search (cpd_kernels.hip "CPD-heuristic search"): one search
 // per query (sorted by target row, qrow as for table-search) over the dense
 // move rows (2^lb bits per column); adj_f / adj_w: packed adjacency with

@@ -7,6 +7,8 @@
 //             [--index auto|rle|dense] [--read-threads T] [--parse-threads P]
 //             [--paths]  (table-search only: also write every walk's nodes)
 //             [--search-paths]  (cpd-search only: also write every route's nodes)
+//             [--costs [--slice-moves S]]  (table-search only: cost every walk
+//                                           under the request's list of diffs)
 //             [--verbose]  (per request on stderr: read+parse / prepare / compute)
 //
 // Creates its request FIFO, streams the CPD buckets this worker owns onto its
@@ -40,6 +42,16 @@
 // cpd_query_search_paths and <query file>.paths holds the search paths in
 // the same format: the A* tree's chain from s to the incumbent's node, then
 // the CPD walk to t; "s t 0 0" (no nodes) for a query without a route.
+// With --costs (table-search only) the request's third field may be a
+// comma-separated list of up to 8 diff files, "-" = free flow (e.g.
+// "-,a.diff,b.diff"); the walk runs once (cpd_query_costs) and <query
+// file>.res gets "s t moves finished cost_0 ... cost_{C-1}" per query in file
+// order (written as .res.tmp, renamed into place): C = the number of diffs,
+// cost_j the walk's cost under diff j — or, with --slice-moves S, C = 1: move
+// h of a walk costed under diff min(h / S, last), a trip replanned every S
+// moves.  The answer line keeps its 10 fields and carries no cost.  A
+// request's "debug": true writes nothing more with --costs: <query file>.res
+// is the costs file.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -154,6 +166,32 @@ static void write_paths(cpd_index* ix, const std::string& qfile, const std::vect
     }
 }
 
+// <query file>.res of a --costs request: s t moves finished cost_0 ... per query
+static void write_costs(cpd_index* ix, const std::string& qfile, const std::vector<uint32_t>& s,
+                        const std::vector<uint32_t>& t, size_t cols) {
+    const size_t nq = s.size();
+    std::vector<uint64_t> costs(nq * cols);
+    std::vector<uint32_t> hops(nq);
+    std::vector<uint8_t> fin(nq);
+    if (cpd_query_costs_fetch(ix, costs.data(), hops.data(), fin.data()) != CPD_OK)
+        throw std::runtime_error(cpd_last_error());
+    const std::string path = qfile + ".res", tmp = path + ".tmp";
+    std::FILE* f = std::fopen(tmp.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    bool ok = true;
+    for (size_t q = 0; q < nq && ok; ++q) {
+        ok = std::fprintf(f, "%u %u %u %u", s[q], t[q], hops[q], fin[q] == 1 ? 1u : 0u) > 0;
+        for (size_t j = 0; j < cols && ok; ++j)
+            ok = std::fprintf(f, " %llu", (unsigned long long)costs[q * cols + j]) > 0;
+        ok = ok && std::fputc('\n', f) != EOF;
+    }
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
+        ::unlink(tmp.c_str());
+        throw std::runtime_error("cannot write " + path);
+    }
+}
+
 static bool write_answer(const std::string& path, const std::string& line) {
     // process_query.send_remote mkfifo's the answer before writing the request
     // (process_query.py:72-73); tolerate a late mkfifo for up to 10 s
@@ -198,7 +236,17 @@ int main(int argc, char** argv) {
                      "       [--search-paths]  cpd-search only: answer through "
                      "cpd_query_search_paths and\n"
                      "                  write every route's nodes to <query file>.paths, same "
-                     "format\n");
+                     "format\n"
+                     "       [--costs [--slice-moves S]]  table-search only: the request's diff "
+                     "field may list\n"
+                     "                  up to 8 diffs (\"-,a.diff,b.diff\"); one walk costs every "
+                     "query under each\n"
+                     "                  (cpd_query_costs) and <query file>.res gets, per query:\n"
+                     "                  s t moves finished cost_0 ... cost_{C-1}\n"
+                     "                  (with --slice-moves S one cost: move h under diff "
+                     "min(h / S, last));\n"
+                     "                  \"debug\": true in a request adds nothing: .res is the "
+                     "costs file\n");
         return 2;
     }
     // table-search (make_fifos.py:20) or the CPD-heuristic search
@@ -219,6 +267,18 @@ int main(int argc, char** argv) {
     if (search_paths && !search) {
         std::fprintf(stderr, "fifo_auto: --search-paths needs --alg cpd-search (the walks of a "
                              "table-search are extracted with --paths)\n");
+        return 2;
+    }
+    const bool costs = a.has("costs");
+    if (costs && (search || paths)) {
+        std::fprintf(stderr, "fifo_auto: --costs needs --alg table-search without --paths (a "
+                             "cpd-search's route depends on the weights; --paths answers through "
+                             "cpd_query_paths)\n");
+        return 2;
+    }
+    const long long slice_moves = a.num("slice-moves", 0);
+    if ((slice_moves && !costs) || slice_moves < 0 || slice_moves > 0xFFFFFFFFll) {
+        std::fprintf(stderr, "fifo_auto: --slice-moves S needs --costs and 0 <= S < 2^32\n");
         return 2;
     }
     int mcode = cli::method_code(method);
@@ -256,6 +316,8 @@ int main(int argc, char** argv) {
     cpd::io::XYGraph g;
     std::map<std::string, std::vector<uint32_t>> diff_cache;
     std::string active_diff = "-";
+    std::string active_sets;  // --costs: the diff list whose sets are loaded
+    size_t active_nsets = 0;
     int device = -1;
     bool arena = false;
     try {
@@ -481,7 +543,36 @@ int main(int argc, char** argv) {
             static std::vector<uint32_t> s, t;
             cpd::io::read_query_file(qfile, parse_threads, s, t);
             const double t_read = now() - t0;
-            if (diff != active_diff) {
+            if (costs) {
+                // the diff field is a list: its sets, loaded beside (and
+                // independent of) the index's current weights
+                if (diff != active_sets) {
+                    std::vector<const uint32_t*> sets;
+                    for (size_t p0 = 0; p0 <= diff.size();) {
+                        size_t p1 = diff.find(',', p0);
+                        if (p1 == std::string::npos) p1 = diff.size();
+                        const std::string name = diff.substr(p0, p1 - p0);
+                        if (name.empty()) throw std::runtime_error("empty name in diff list '" + diff + "'");
+                        if (sets.size() == CPD_MAX_WEIGHT_SETS)
+                            throw std::runtime_error("more than " + std::to_string(CPD_MAX_WEIGHT_SETS) +
+                                                     " diffs in '" + diff + "'");
+                        if (name == "-") {
+                            sets.push_back(nullptr);
+                        } else {
+                            auto it = diff_cache.find(name);
+                            if (it == diff_cache.end())
+                                it = diff_cache.emplace(name, cpd::io::read_diff(name, g)).first;
+                            sets.push_back(it->second.data());
+                        }
+                        p0 = p1 + 1;
+                    }
+                    active_sets.clear();
+                    if (cpd_index_set_weight_sets(ix, (uint32_t)sets.size(), sets.data()) != CPD_OK)
+                        throw std::runtime_error(cpd_last_error());
+                    active_sets = diff;
+                    active_nsets = sets.size();
+                }
+            } else if (diff != active_diff) {
                 if (diff == "-" ) {
                     cli::check(cpd_index_set_weights(ix, nullptr), "weights");
                 } else {
@@ -511,6 +602,10 @@ int main(int argc, char** argv) {
                 if (ss.overflow)
                     std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
                                  (unsigned long long)ss.overflow);
+            } else if (costs) {
+                rc = cpd_query_costs(ix, k_moves, (uint32_t)slice_moves, &st);
+                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                write_costs(ix, qfile, s, t, slice_moves ? 1u : active_nsets);
             } else if (paths) {
                 static std::vector<uint64_t> poff;
                 poff.resize(nq + 1);
@@ -521,7 +616,7 @@ int main(int argc, char** argv) {
                 rc = cpd_query_run(ix, k_moves, &st);
                 if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
             }
-            if (debug) {
+            if (debug && !costs) {
                 std::vector<uint64_t> cost(nq);
                 std::vector<uint32_t> hops(nq);
                 std::vector<uint8_t> fin(nq);

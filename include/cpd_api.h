@@ -416,6 +416,48 @@ int  cpd_query_paths(cpd_index* ix, int32_t k_moves, uint64_t* offsets /* nq+1 *
  * CPD_E_ARG before any of the two on the prepared queries, or for a range
  * past nq.                                                                   */
 int  cpd_query_paths_fetch(cpd_index* ix, uint32_t first, uint32_t count, uint32_t* nodes);
+
+/* Costs under several weight sets in ONE walk — what the reference pays one
+ * experiment per diff for (process_query.py:178 sends the whole scenario to
+ * the workers again for every congestion file of `diffs`; args.py -k: "extract
+ * the first k moves, then replan" under the next one).  The table-search
+ * route never depends on the weights, so the walk is taken once and every
+ * edge on it is summed under each set.
+ * cpd_index_set_weight_sets: nsets (<= CPD_MAX_WEIGHT_SETS) arrays of m
+ * weights in original edge order, as cpd_index_set_weights takes one; w[j] ==
+ * NULL = the free-flow weights (the "-" diff); nsets == 0 clears the sets.
+ * CPD_E_ARG for more sets, or w == NULL with nsets > 0.  The sets are copied,
+ * permuted to column space and kept in HBM — 16 B per adjacency slot for up
+ * to 4 sets, 32 B above — until replaced, cleared or cpd_index_free.  They
+ * are independent of the index's current weights: cpd_index_set_weights,
+ * cpd_query_run, cpd_query_paths and cpd_query_search neither see nor change
+ * them, and a call here leaves the search's tables as they are.
+ * cpd_query_costs: on the queries of the last cpd_query_prepare, the walk of
+ * cpd_query_run (k_moves with its meaning, the n-move loop guard, and the
+ * k_moves = 0 refill limit described at cpd_query_paths).
+ *   slice_moves == 0: the cost of every walk under every set, C = nsets
+ *     values per query;
+ *   slice_moves == S > 0: C = 1 value per query; move number h of the walk
+ *     (0-based) is costed under set min(h / S, nsets - 1): the cost of a trip
+ *     replanned every S moves under successive weight sets.
+ * st: queries / finished / hops as cpd_query_run reports them, cost = the sum
+ * of set 0's column (slice_moves == 0) or of the one column, kernel_ms of
+ * this walk.  CPD_E_ARG when no sets are loaded or the index is incomplete.
+ * The results live in buffers of their own: what cpd_query_fetch and
+ * cpd_query_paths_fetch return is left as it was.
+ * cpd_query_costs_fetch: costs[q * C + j] in the CALLER's query order (sums
+ * are 64-bit: weights up to 0xFFFFFFFF never wrap), hops and finished as the
+ * walk's; any pointer may be NULL; scattered to the caller's order on the GPU
+ * as cpd_query_fetch does.  CPD_E_ARG before a cpd_query_costs on the
+ * prepared queries.
+ * When a device arena is committed the set table and the result buffers are
+ * carved from it; the arena never takes a buffer back, so a table or batch
+ * larger than any before it on this index uses up that many more arena bytes
+ * until cpd_device_arena_release (what does not fit is allocated separately). */
+#define CPD_MAX_WEIGHT_SETS 8u
+int  cpd_index_set_weight_sets(cpd_index* ix, uint32_t nsets, const uint32_t* const* w);
+int  cpd_query_costs(cpd_index* ix, int32_t k_moves, uint32_t slice_moves, cpd_query_stats* st);
+int  cpd_query_costs_fetch(cpd_index* ix, uint64_t* costs, uint32_t* hops, uint8_t* finished);
 void cpd_index_free(cpd_index* ix);
 
 /* [gpu] CPD-heuristic search — fifo_auto's other algorithm family
