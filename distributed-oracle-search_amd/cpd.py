@@ -35,6 +35,8 @@ PART_MOD = 1
 INF = 0xFFFFFFFF
 FM_ALL = 0xFFFF
 MAX_WEIGHT_SETS = 8
+MAX_LOAD_SLICES = 8
+LOADS_ACCUMULATE = 1
 
 EXPORTED = [
     "cpd_last_error", "cpd_version", "cpd_partition", "cpd_partition_nbuckets",
@@ -57,6 +59,7 @@ EXPORTED = [
     "cpd_rows_move_bits", "cpd_graph_move_bits", "cpd_bucket_bytes", "cpd_space_check",
     "cpd_query_paths", "cpd_query_paths_fetch", "cpd_query_search_paths",
     "cpd_index_set_weight_sets", "cpd_query_costs", "cpd_query_costs_fetch",
+    "cpd_query_loads", "cpd_query_loads_fetch", "cpd_query_loads_clear",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
@@ -547,6 +550,7 @@ class Index:
         self.graph = graph
         self._nq, self._path_offsets = 0, None  # prepared queries; offsets of their paths
         self._nsets, self._cost_cols = 0, None  # weight sets loaded; columns of the last costs_run
+        self._load_slices = None                # slices of the resident load table
         self._h = C.c_void_p()
         if _handle is not None:
             self._h = _handle
@@ -729,6 +733,53 @@ class Index:
         _check(lib.cpd_query_costs_fetch(self._h, _ptr(costs, u64p), _ptr(hops, u32p),
                                          _ptr(fin, u8p)))
         return costs, hops, fin
+
+    def loads(self, s, t, demand=None, k_moves: int = -1, slices: int = 1, slice_moves: int = 0,
+              accumulate: bool = False):
+        """The demand every edge carries when the table-search walks of (s, t)
+        are routed (cpd_query_loads): (loads u64[slices, m], stats).  demand:
+        one u32 per query (None = 1 each), added to loads[j, e] for every move
+        of the query's walk, e = the original index of the edge taken (the
+        index set_weights() uses), j = min(h // slice_moves, slices - 1) for
+        move number h (slices = 1: j = 0, slice_moves = 0).  accumulate=True
+        adds to the table earlier calls on this index left."""
+        self.prepare(s, t)
+        st = self.loads_run(demand, k_moves, slices, slice_moves, accumulate)
+        return self.loads_fetch(), st
+
+    def loads_run(self, demand=None, k_moves: int = -1, slices: int = 1, slice_moves: int = 0,
+                  accumulate: bool = False) -> dict:
+        """cpd_query_loads on the prepared queries: stats (cost / hops /
+        finished of this walk then come from cpd_query_fetch)."""
+        self._path_offsets = None
+        d = None
+        if demand is not None:
+            d = _u32(demand)
+            if d.shape != (self._nq,):
+                raise ValueError("demand must have one entry per prepared query")
+        st = QueryStats()
+        _check(lib.cpd_query_loads(self._h, C.c_int32(k_moves), _ptr(d, u32p), C.c_uint32(slices),
+                                   C.c_uint32(slice_moves),
+                                   C.c_uint32(LOADS_ACCUMULATE if accumulate else 0), C.byref(st)))
+        self._load_slices = slices
+        return {k: getattr(st, k) for k, _ in QueryStats._fields_}
+
+    def loads_fetch(self) -> np.ndarray:
+        """loads u64[slices, m] of the resident table (cpd_query_loads_fetch).
+        The library copies slices * m values, so this refuses (CPD_E_ARG, as
+        the library would) when no loads_run() has made a table since the
+        index was created or cleared."""
+        if self._load_slices is None:
+            raise CpdError(CPD_E_ARG, "loads fetch: no loads() / loads_run() on this index since "
+                                      "it was made or cleared")
+        out = np.empty((self._load_slices, self.graph.plan.info()["m"]), np.uint64)
+        _check(lib.cpd_query_loads_fetch(self._h, _ptr(out, u64p)))
+        return out
+
+    def loads_clear(self) -> None:
+        """Drop the resident load table (cpd_query_loads_clear)."""
+        _check(lib.cpd_query_loads_clear(self._h))
+        self._load_slices = None
 
     def search(self, s, t, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
                capacity=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,

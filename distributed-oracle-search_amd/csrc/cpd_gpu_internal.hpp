@@ -125,6 +125,7 @@ struct cpd_graph {
     std::vector<uint32_t> inv;         // column -> node
     DevBuf<uint32_t> order_d;          // node -> column (query preparation)
     DevBuf<uint32_t> inv_d;            // column -> node (path extraction; at first use)
+    DevBuf<uint32_t> slot_of_edge_d;   // file edge -> adjacency slot (edge loads; at first use)
     std::vector<uint32_t> edge_perm;   // column-space edge -> file edge
     std::vector<uint32_t> w_free_col;  // free-flow weights, column-space edges
     std::vector<uint32_t> rowc_host;   // column-space row_ptr (host copy)
@@ -502,6 +503,16 @@ struct cpd_index {
     DevBuf<uint8_t> cs_fin;
     uint32_t cs_cols = 0;
     bool costs_ready = false;
+    // edge loads (cpd_query_loads): the resident table in slot space —
+    // ld_slices planes of n << adj_shift u64 counters, counter (column <<
+    // adj_shift) + move — kept across prepares until cpd_query_loads_clear;
+    // ld_slice_moves: the moves per slice it was filled with (0: one plane);
+    // the batch's demand (caller order) and the fetch's edge-order copy.  The
+    // table is carved from the arena when one is committed (see wsets above).
+    DevBuf<uint64_t> ld_tab, ld_out;
+    DevBuf<uint32_t> ld_demand;
+    uint32_t ld_slices = 0, ld_slice_moves = 0;
+    bool loads_ready = false;
     // search paths (cpd_query_search_paths), scratch of one call, freed when
     // it returns (the cursor stays): the prefix pool and its cursor;
     // per query (sorted order) the prefix's place and length, v* and lw(v*);

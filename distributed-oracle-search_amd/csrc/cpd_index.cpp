@@ -856,6 +856,134 @@ int cpd_query_costs_fetch(cpd_index* ix, uint64_t* costs, uint32_t* hops, uint8_
     });
 }
 
+int cpd_query_loads(cpd_index* ix, int32_t k_moves, const uint32_t* demand, uint32_t nslices,
+                    uint32_t slice_moves, uint32_t flags, cpd_query_stats* st) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        CPD_REQUIRE(nslices >= 1 && nslices <= CPD_MAX_LOAD_SLICES, CPD_E_ARG,
+                    "loads: " + std::to_string(nslices) + " slices, 1 to " +
+                        std::to_string(CPD_MAX_LOAD_SLICES));
+        CPD_REQUIRE((nslices == 1) == (slice_moves == 0), CPD_E_ARG,
+                    "loads: slice_moves must be 0 with one slice and non-zero with more");
+        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
+                    "loads: index incomplete (" + std::to_string(ix->added) + " of " +
+                        std::to_string(ix->nrows) + " rows appended)");
+        const bool keep = (flags & CPD_LOADS_ACCUMULATE) && ix->loads_ready;
+        CPD_REQUIRE(!keep || (ix->ld_slices == nslices && ix->ld_slice_moves == slice_moves),
+                    CPD_E_ARG,
+                    "loads: accumulate into a table of " + std::to_string(ix->ld_slices) +
+                        " slices of " + std::to_string(ix->ld_slice_moves) + " moves asked with " +
+                        std::to_string(nslices) + " of " + std::to_string(slice_moves));
+        cpd_graph* g = ix->g;
+        g->select();
+        hipStream_t s = g->stream;
+        const uint32_t nq = ix->nq;
+        const size_t stride = (size_t)1 << g->adj_shift;
+        // the kernel keeps a slot as u32, 0xFFFFFFFF = none
+        CPD_REQUIRE(stride * g->n < 0xFFFFFFFFull, CPD_E_RANGE, "loads: 2^32 adjacency slots or more");
+        const uint32_t nslots = g->n << g->adj_shift;
+        ix->paths_ready = false;
+        const bool dense = ix->use_dense();
+        if (dense && !ix->dense_ready) ensure_dense(ix);
+        if (!g->slot_of_edge_d.p) {
+            // column-space edge ec of column c sits in slot c * stride + its
+            // place in c's out-list; edge_perm names its file edge
+            std::vector<uint32_t> soe(g->m);
+            for (uint32_t c = 0; c < g->n; ++c)
+                for (uint32_t e = g->rowc_host[c]; e < g->rowc_host[c + 1]; ++e)
+                    soe[g->edge_perm[e]] = (uint32_t)(c * stride + (e - g->rowc_host[c]));
+            g->slot_of_edge_d.upload(soe.data(), soe.size(), s);
+            HIP_CHECK(hipStreamSynchronize(s));  // soe leaves scope
+        }
+        if (!keep) {
+            ix->loads_ready = false;
+            {
+                ArenaScope carve;
+                ix->ld_tab.alloc((size_t)nslices * nslots);
+            }
+            HIP_CHECK(hipMemsetAsync(ix->ld_tab.p, 0, (size_t)nslices * nslots * sizeof(uint64_t), s));
+            ix->ld_slices = nslices;
+            ix->ld_slice_moves = slice_moves;
+            ix->loads_ready = true;
+        }
+        if (demand && nq) ix->ld_demand.upload(demand, nq, s);
+        const uint32_t* dem = demand && nq ? ix->ld_demand.p : nullptr;
+        HIP_CHECK(hipMemsetAsync(ix->agg.p, 0, 3 * sizeof(unsigned long long), s));
+        Events<2> ev(g);
+        const hipEvent_t a = ev.e[0], b = ev.e[1];
+        HIP_CHECK(hipEventRecord(a, s));
+        const uint32_t* adj = ix->custom_w ? ix->adj_sel.p : g->adj.p;
+        (void)hipGetLastError();
+        if (nq && dense)
+            launch_table_loads_dense(adj, g->adj_shift, ix->dense.p, g->npad, g->tlb, ix->qs.p,
+                                     ix->qt.p, ix->qrow.p, ix->qperm.p, dem, nq, k_moves, g->n,
+                                     nslices, slice_moves, ix->ld_tab.p, ix->cost.p, ix->hops.p,
+                                     ix->fin.p, ix->agg.p, s);
+        else if (nq)
+            launch_table_loads(adj, g->adj_shift, ix->off.p, ix->runs.p, ix->qs.p, ix->qt.p,
+                               ix->qrow.p, ix->qperm.p, dem, nq, k_moves, g->n, nslices,
+                               slice_moves, ix->ld_tab.p, ix->cost.p, ix->hops.p, ix->fin.p,
+                               ix->agg.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(b, s));
+        unsigned long long hagg[3] = {0, 0, 0};  // finished, moves, cost (wave_stats)
+        HIP_CHECK(hipMemcpyAsync(hagg, ix->agg.p, sizeof hagg, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+        if (g->timing) {
+            // the walk's bytes + a demand and its index per query + one
+            // 8-B counter per move
+            Agg& ag = g->agg[dense ? "table_loads_dense" : "table_loads"];
+            ag.launches++;
+            ag.ms += ms;
+            ag.bytes += walk_model_bytes(ix, dense, nq, hagg[1]) + (dem ? 8.0 : 0.0) * nq +
+                        8.0 * (double)hagg[1];
+        }
+        if (st) {
+            st->queries = nq;
+            st->finished = hagg[0];
+            st->hops = hagg[1];
+            st->cost = hagg[2];
+            st->kernel_ms = ms;
+        }
+    });
+}
+
+int cpd_query_loads_fetch(cpd_index* ix, uint64_t* loads) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        CPD_REQUIRE(ix->loads_ready, CPD_E_ARG,
+                    "loads fetch: no cpd_query_loads on this index since it was made or cleared");
+        cpd_graph* g = ix->g;
+        const size_t total = (size_t)ix->ld_slices * g->m;
+        if (!total) return;
+        CPD_REQUIRE(loads, CPD_E_ARG, "loads fetch: null argument");
+        g->select();
+        hipStream_t s = g->stream;
+        // slot space -> original edge order, on the GPU, then copied out once
+        ix->ld_out.alloc(total);
+        (void)hipGetLastError();
+        launch_loads_gather(ix->ld_tab.p, g->slot_of_edge_d.p, g->m, g->n << g->adj_shift,
+                            ix->ld_slices, ix->ld_out.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(loads, ix->ld_out.p, total * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int cpd_query_loads_clear(cpd_index* ix) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        ix->g->select();
+        ix->ld_tab.release();
+        ix->ld_out.release();
+        ix->ld_slices = ix->ld_slice_moves = 0;
+        ix->loads_ready = false;
+    });
+}
+
 int cpd_query_fetch(cpd_index* ix, uint64_t* cost, uint32_t* hops, uint8_t* finished) {
     return guarded([&] {
         CPD_REQUIRE(ix, CPD_E_ARG, "null index");

@@ -3363,6 +3363,210 @@ __global__ __launch_bounds__(256) void table_walk_costs(
                                      slice, costs_out, hops_out, fin_out, agg);
 }
 
+// Edge loads (cpd_query_loads): table_walk's walk once, adding the query's
+// demand to a counter per (time slice, adjacency slot) for every move taken.
+// The frame (a wave owns a chunk, lanes are refilled), the retire condition
+// and walk_begin / walk_move are table_walk's, and the cost is summed from the
+// adjacency the walk was given, so cost, hops, finished and the route are the
+// plain walk's.
+// tab is in slot space: counter j * nslots + (col << SHIFT) + move, nslots =
+// n << SHIFT, u64 (loads_gather below permutes it to edge order for the
+// fetch).  A lane reads its query's demand once, when it begins the query
+// (demand is in the caller's order: through qperm; NULL = 1 each).  SLICED:
+// move h of a walk counts in slice min(h / slice, nslices - 1), kept per lane
+// as a slice index and a countdown as costs_walk keeps its set, no division.
+// The add is a relaxed agent-scope atomic whose result is not used (one
+// no-return 8-B atomic).  The hop that makes a move never waits for its add:
+// the move taken in one iteration is kept (pslot, pset, pdem) and added in the
+// next, AFTER that iteration's own loads (adjacency row, move word or first
+// run probe; wide adjacency: the edge) are issued.  A lane that retires leaves
+// its last move pending like any other — pdem is the demand of the query that
+// took the move, not of the one the lane holds now — and what is pending when
+// the chunk runs dry is added after the loop.
+// What the ISA does with it: only lanes that took a move add, so the atomic
+// sits behind a branch, and hipcc waits for the hop's loads with s_waitcnt
+// vmcnt(0) after the join — the NEXT hop's loads are waited for together with
+// the add issued behind them.  An add that every lane issues (a lane without
+// a move adds 0 to the counter of its last move) has no branch and gets the
+// counted wait, vmcnt(1), the atomic left outstanding; it was built and
+// measured (DESIGN §3 "Edge loads", profiles/loads/loads_ab_uncond_*.json):
+// 15% slower on dense and on RLE rows, because the kernel is bound by the
+// number of atomic requests, not by their latency, and the idle lanes' adds
+// are requests too.  So the guarded add stays.
+// Every walking lane issues its own add.  Merging the adds of a wave's lanes
+// that hold the same counter in the same iteration (readfirstlane of an
+// unmerged lane's key, ballot of the equal lanes, their demands summed, one
+// lane adds; 4 rounds) was built and measured beside it (DESIGN §3 "Edge
+// loads", profiles/loads/): on the bench's 1M-query mix it removed 0.03% of
+// the L2 atomic requests — walks that share a suffix reach it in different
+// iterations — and was 1% slower on dense rows, equal on RLE rows; removed.
+// The kernel runs at the chip's rate for scattered atomics: one 64-B fabric
+// request per move.
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+
+// The add of one lane: counter (pset, pslot) += pdem (pslot == kNoSlot: none).
+__device__ __forceinline__ void loads_add(unsigned long long* __restrict__ tab, uint32_t nslots,
+                                          uint32_t pslot, uint32_t pset, uint32_t pdem) {
+    if (pslot != kNoSlot)
+        (void)__hip_atomic_fetch_add(tab + ((size_t)pset * nslots + pslot),
+                                     (unsigned long long)pdem, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int SHIFT, bool SLICED, class Rows>
+__device__ __forceinline__ void loads_walk(
+    const uint2* __restrict__ adj, Rows rows, const uint32_t* __restrict__ qs,
+    const uint32_t* __restrict__ qt, const uint32_t* __restrict__ qrow,
+    const uint32_t* __restrict__ qperm, const uint32_t* __restrict__ demand, uint32_t nq,
+    uint32_t chunk, uint32_t limit, uint32_t nslots, uint32_t nslices, uint32_t slice,
+    unsigned long long* __restrict__ tab, uint64_t* __restrict__ cost_out,
+    uint32_t* __restrict__ hops_out, uint8_t* __restrict__ fin_out,
+    unsigned long long* __restrict__ agg) {
+    constexpr bool kDense = std::is_same<Rows, DenseRows>::value;
+    constexpr int NQ = SHIFT == 2 ? 2 : 1;  // 16-B pieces of an adjacency row
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t q0l = wave * chunk;
+    const uint32_t q0 = q0l < nq ? (uint32_t)q0l : nq;
+    const uint32_t q1 = (uint32_t)min((uint64_t)nq, q0l + chunk);
+    uint64_t sum_cost = 0;
+    uint32_t sum_hops = 0, sum_fin = 0;
+    uint32_t dem = 0;                               // the demand of the lane's query
+    uint32_t pslot = kNoSlot, pset = 0, pdem = 0;   // the last iteration's move, not yet added
+    uint32_t set = 0, left = slice;  // sliced: the slice of the next move, moves left in it
+    WalkState w;
+    uint32_t next = q0;  // wave-uniform: first query of the chunk not yet started
+    w.q = kIdleQ;        // idle: column 0 of row 0 stays loadable
+    w.cur = 0;
+    w.t = 0;
+    w.hops = 0;
+    w.bad = false;
+    w.cost = 0;
+    w.pos = 0;
+    w.R = 0;
+    w.row = rows_base(rows);
+    auto begin = [&](uint32_t q) {
+        walk_begin(w, q, qs, qt, qrow, rows);
+        dem = demand ? demand[qperm[q]] : 1u;
+        // the walk's state is in registers, no load of it pending (costs_walk's settle)
+        if constexpr (kDense) asm volatile("" ::"v"(w.cur), "v"(w.t), "v"(w.row), "v"(dem));
+        else asm volatile("" ::"v"(w.cur), "v"(w.t), "v"(w.row), "v"(w.R), "v"(dem));
+    };
+    if (next + lane < q1) begin(next + lane);
+    next = min(q1, next + 64u);
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    for (;;) {
+        // retire finished walks; their lanes take the next queries of the chunk
+        const bool idle = w.q == kIdleQ;
+        const bool done = !idle && (w.cur == w.t || w.hops >= limit || w.bad);
+        const uint64_t m = __ballot(done);
+        if (m) {
+            if (done) {
+                const uint32_t fin = w.cur == w.t ? 1u : 0u;
+                cost_out[w.q] = w.cost;
+                hops_out[w.q] = w.hops;
+                fin_out[w.q] = (uint8_t)fin;
+                sum_cost += w.cost;
+                sum_hops += w.hops;
+                sum_fin += fin;
+                set = 0;
+                left = slice;
+                const uint32_t nqi = next + (uint32_t)__builtin_popcountll(m & lt_mask);
+                if (nqi < q1) begin(nqi);
+                else w.q = kIdleQ;
+            }
+            next = min(q1, next + (uint32_t)__builtin_popcountll(m));
+        }
+        if (!__any(w.q != kIdleQ)) break;
+        // this hop's loads that depend on cur alone, for every lane (an idle
+        // or arrived lane stands on a valid column of a valid row)
+        uint4 p[NQ];
+        uint32_t word;
+        if (SHIFT == 0) {
+            const uint2 e = adj[w.cur];
+            p[0] = make_uint4(e.x, e.y, kNoEdge, 0u);
+        } else if (SHIFT <= 2) {
+            const uint4* a4 = reinterpret_cast<const uint4*>(adj) + (size_t)w.cur * NQ;
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) p[k] = a4[k];
+        }
+        if constexpr (kDense) word = w.row[w.cur >> (5u - rows.tb.lb)];
+        else word = w.row[w.pos];  // the run search's first probe
+        if (SHIFT <= 2) {  // the last iteration's move, behind them
+            __builtin_amdgcn_sched_barrier(0);
+            loads_add(tab, nslots, pslot, pset, pdem);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const bool walking = w.q != kIdleQ && w.cur != w.t;
+        uint32_t mv;
+        if constexpr (kDense) {
+            const uint32_t cm = 31u >> rows.tb.lb, mm = (1u << (1u << rows.tb.lb)) - 1u;
+            mv = (word >> ((w.cur & cm) << rows.tb.lb)) & mm;
+        } else {
+            mv = word & 0xFu;
+            if (walking) mv = walk_move(w, rows);
+        }
+        const bool slot_ok = (mv >> SHIFT) == 0u;  // else: names no slot of cur, malformed row
+        const uint32_t slot = mv & ((1u << SHIFT) - 1u);
+        uint32_t ex, ew;
+        if (SHIFT <= 2) {
+            const uint4 e = (NQ == 2 && (slot & 2u)) ? p[NQ - 1] : p[0];
+            ex = (slot & 1u) ? e.z : e.x;
+            ew = (slot & 1u) ? e.w : e.y;
+        } else {  // wide adjacency: the edge load follows the move, the add follows it
+            const uint2 e = adj[((size_t)w.cur << SHIFT) + slot];
+            __builtin_amdgcn_sched_barrier(0);
+            loads_add(tab, nslots, pslot, pset, pdem);
+            __builtin_amdgcn_sched_barrier(0);
+            ex = e.x;
+            ew = e.y;
+        }
+        const bool step = walking && slot_ok && ex != kNoEdge;
+        w.bad = w.bad || (walking && !step);
+        pslot = step ? (w.cur << SHIFT) + slot : kNoSlot;
+        pset = set;
+        pdem = dem;
+        if constexpr (SLICED) {
+            if (step && --left == 0u) {
+                left = slice;
+                if (set + 1u < nslices) ++set;
+            }
+        }
+        if (step) {
+            w.cost += ew;
+            w.cur = ex;
+            ++w.hops;
+        }
+    }
+    loads_add(tab, nslots, pslot, pset, pdem);  // the chunk's last moves
+    wave_stats(sum_cost, sum_hops, sum_fin, agg);
+}
+
+template <int SHIFT, class Rows, bool SLICED>
+__global__ __launch_bounds__(256) void table_walk_loads(
+    const uint2* __restrict__ adj, Rows rows, const uint32_t* __restrict__ qs,
+    const uint32_t* __restrict__ qt, const uint32_t* __restrict__ qrow,
+    const uint32_t* __restrict__ qperm, const uint32_t* __restrict__ demand, uint32_t nq,
+    uint32_t chunk, uint32_t limit, uint32_t nslots, uint32_t nslices, uint32_t slice,
+    unsigned long long* __restrict__ tab, uint64_t* __restrict__ cost_out,
+    uint32_t* __restrict__ hops_out, uint8_t* __restrict__ fin_out,
+    unsigned long long* __restrict__ agg) {
+    loads_walk<SHIFT, SLICED>(adj, rows, qs, qt, qrow, qperm, demand, nq, chunk, limit,
+                              nslots, nslices, slice, tab, cost_out, hops_out, fin_out, agg);
+}
+
+// The fetch order of the load table: out[j * m + e] = tab[j * nslots +
+// slot_of_edge[e]], a lane per (slice, edge).
+__global__ __launch_bounds__(256) void loads_gather(const unsigned long long* __restrict__ tab,
+                                                    const uint32_t* __restrict__ slot_of_edge,
+                                                    uint32_t m, uint32_t nslots, uint32_t nslices,
+                                                    uint64_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint64_t)m * nslices) return;
+    const uint32_t j = (uint32_t)(i / m), e = (uint32_t)(i - (uint64_t)j * m);
+    out[i] = tab[(size_t)j * nslots + slot_of_edge[e]];
+}
+
 __device__ void wave_stats(uint64_t cost, uint32_t hops, uint32_t fin,
                            unsigned long long* __restrict__ agg) {
     // wave reduction, one atomic per wave per counter
@@ -4870,8 +5074,8 @@ void launch_expand_rows(const uint64_t* offsets, const uint32_t* runs, const uin
 // ran out of workgroup slots: 8.2M against 11.4M; profiles/walk_wpb_ab/).
 constexpr uint32_t kDenseWaves = 1024, kDenseWpb = 1, kRleWaves = 8192, kRleWpb = 4;
 
-// The launch shape of the three walks (table_walk, table_walk_paths,
-// table_walk_costs): queries per wave and the grid for them.
+// The launch shape of the walks (table_walk, table_walk_paths,
+// table_walk_costs, table_walk_loads): queries per wave and the grid for them.
 struct WalkShape {
     uint32_t chunk;
     dim3 grid, blk;
@@ -5034,6 +5238,71 @@ void launch_table_costs(const uint32_t* adj, uint32_t shift, const uint64_t* off
     launch_walk_costs(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs},
                       wsets, nsets, slice, qs, qt, qrow, nq, n, walk_limit(kmoves, n), costs, hops,
                       fin, agg, kRleWaves, 1u << 30, s, kRleWpb);
+}
+
+// Edge loads: launch_walk's chunking with the walk's own constants
+// (kDenseWaves / kDenseWpb, kRleWaves / kRleWpb).
+template <class Rows>
+static void launch_walk_loads(const uint2* adj, uint32_t shift, const Rows& rows,
+                              const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
+                              const uint32_t* qperm, const uint32_t* demand, uint32_t nq,
+                              uint32_t n, uint32_t limit, uint32_t nslices, uint32_t slice,
+                              uint64_t* tab, uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                              unsigned long long* agg, uint32_t waves_target, uint32_t chunk_max,
+                              hipStream_t s, uint32_t wpb) {
+    const WalkShape sh = walk_shape(nq, waves_target, chunk_max, wpb);
+    const dim3 grid = sh.grid, blk = sh.blk;
+    const uint32_t c = sh.chunk;
+    const uint32_t nslots = n << shift;
+    unsigned long long* t = reinterpret_cast<unsigned long long*>(tab);
+#define CPD_WALK_LOADS_F(SH, SL)                                                              \
+    launch(kern::table_walk_loads<SH, Rows, SL>, grid, blk, s, adj, rows, qs, qt, qrow, qperm, \
+           demand, nq, c, limit, nslots, nslices, slice, t, cost, hops, fin, agg)
+#define CPD_WALK_LOADS(SH)                         \
+    do {                                           \
+        if (slice) CPD_WALK_LOADS_F(SH, true);     \
+        else CPD_WALK_LOADS_F(SH, false);          \
+    } while (0)
+    switch (shift) {
+        case 0: CPD_WALK_LOADS(0); break;
+        case 1: CPD_WALK_LOADS(1); break;
+        case 2: CPD_WALK_LOADS(2); break;
+        case 3: CPD_WALK_LOADS(3); break;
+        default: CPD_WALK_LOADS(4); break;
+    }
+#undef CPD_WALK_LOADS
+#undef CPD_WALK_LOADS_F
+}
+
+void launch_table_loads_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                              uint32_t npad, uint32_t lb, const uint32_t* qs, const uint32_t* qt,
+                              const uint32_t* qrow, const uint32_t* qperm, const uint32_t* demand,
+                              uint32_t nq, int32_t kmoves, uint32_t n, uint32_t nslices,
+                              uint32_t slice, uint64_t* tab, uint64_t* cost, uint32_t* hops,
+                              uint8_t* fin, unsigned long long* agg, hipStream_t s) {
+    const kern::DenseRows rows{dense, npad >> (5u - lb), kern::Tbl{lb}};
+    launch_walk_loads(reinterpret_cast<const uint2*>(adj), shift, rows, qs, qt, qrow, qperm, demand,
+                      nq, n, walk_limit(kmoves, n), nslices, slice, tab, cost, hops, fin, agg,
+                      kDenseWaves, 1024u, s, kDenseWpb);
+}
+
+void launch_table_loads(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                        const uint32_t* runs, const uint32_t* qs, const uint32_t* qt,
+                        const uint32_t* qrow, const uint32_t* qperm, const uint32_t* demand,
+                        uint32_t nq, int32_t kmoves, uint32_t n, uint32_t nslices, uint32_t slice,
+                        uint64_t* tab, uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                        unsigned long long* agg, hipStream_t s) {
+    launch_walk_loads(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs}, qs,
+                      qt, qrow, qperm, demand, nq, n, walk_limit(kmoves, n), nslices, slice, tab,
+                      cost, hops, fin, agg, kRleWaves, 1u << 30, s, kRleWpb);
+}
+
+void launch_loads_gather(const uint64_t* tab, const uint32_t* slot_of_edge, uint32_t m,
+                         uint32_t nslots, uint32_t nslices, uint64_t* out, hipStream_t s) {
+    const uint64_t total = (uint64_t)m * nslices;
+    if (!total) return;
+    launch(kern::loads_gather, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), s,
+           reinterpret_cast<const unsigned long long*>(tab), slot_of_edge, m, nslots, nslices, out);
 }
 
 // Path offsets: lens[q] = hops[q] + 1 (caller order), lens[nq] = 0, then an

@@ -284,6 +284,27 @@ void launch_table_costs(const uint32_t* adj, uint32_t shift, const uint64_t* off
                         const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow, uint32_t nq,
                         int32_t kmoves, uint32_t n, uint64_t* costs, uint32_t* hops, uint8_t* fin,
                         unsigned long long* agg, hipStream_t s);
+// Edge loads (cpd_query_loads): the table-search walk once, adding demand[
+// qperm[q]] (NULL: 1) for every move of sorted query q to tab[j * nslots +
+// (column << shift) + move], nslots = n << shift, j = min(h / slice, nslices -
+// 1) for move number h (slice == 0: j = 0).  The caller zeroes tab or keeps
+// what earlier launches left.  cost / hops / fin / agg as launch_table_search
+// writes them.  launch_loads_gather: out[j * m + e] = tab[j * nslots +
+// slot_of_edge[e]].
+void launch_table_loads_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                              uint32_t npad, uint32_t lb, const uint32_t* qs, const uint32_t* qt,
+                              const uint32_t* qrow, const uint32_t* qperm, const uint32_t* demand,
+                              uint32_t nq, int32_t kmoves, uint32_t n, uint32_t nslices,
+                              uint32_t slice, uint64_t* tab, uint64_t* cost, uint32_t* hops,
+                              uint8_t* fin, unsigned long long* agg, hipStream_t s);
+void launch_table_loads(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                        const uint32_t* runs, const uint32_t* qs, const uint32_t* qt,
+                        const uint32_t* qrow, const uint32_t* qperm, const uint32_t* demand,
+                        uint32_t nq, int32_t kmoves, uint32_t n, uint32_t nslices, uint32_t slice,
+                        uint64_t* tab, uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                        unsigned long long* agg, hipStream_t s);
+void launch_loads_gather(const uint64_t* tab, const uint32_t* slot_of_edge, uint32_t m,
+                         uint32_t nslots, uint32_t nslices, uint64_t* out, hipStream_t s);
 // out[perm[i] * k + j] = in[i * k + j] (k u64 per query, to the caller's order)
 void launch_scatter_u64_rows(const uint64_t* in, const uint32_t* perm, uint32_t nq, uint32_t k,
                              uint64_t* out, hipStream_t st);

@@ -9,6 +9,8 @@
 //             [--search-paths]  (cpd-search only: also write every route's nodes)
 //             [--costs [--slice-moves S]]  (table-search only: cost every walk
 //                                           under the request's list of diffs)
+//             [--loads [--load-slices K --load-slice-moves S]]  (table-search
+//                                           only: also write every edge's load)
 //             [--verbose]  (per request on stderr: read+parse / prepare / compute)
 //
 // Creates its request FIFO, streams the CPD buckets this worker owns onto its
@@ -52,6 +54,14 @@
 // moves.  The answer line keeps its 10 fields and carries no cost.  A
 // request's "debug": true writes nothing more with --costs: <query file>.res
 // is the costs file.
+// With --loads (table-search only) every request is answered through
+// cpd_query_loads with a demand of 1 per query line, not accumulated across
+// requests, and when the answer line arrives <query file>.loads holds one line
+// per edge with any non-zero load, in edge order (the .xy file's):
+// "<edge index> <from> <to> <load_0> ... <load_{K-1}>" — K = 1, or with
+// --load-slices K --load-slice-moves S the K time slices: move h of a walk
+// counts in slice min(h / S, K - 1) (written as .loads.tmp, renamed into
+// place).  The answer line and <query file>.res are what they are without it.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -192,6 +202,33 @@ static void write_costs(cpd_index* ix, const std::string& qfile, const std::vect
     }
 }
 
+// <query file>.loads of a --loads request: edge from to load_0 ... per loaded edge
+static void write_loads(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g,
+                        size_t slices) {
+    std::vector<uint64_t> loads(slices * g.m);
+    if (cpd_query_loads_fetch(ix, loads.data()) != CPD_OK)
+        throw std::runtime_error(cpd_last_error());
+    const std::string path = qfile + ".loads", tmp = path + ".tmp";
+    std::FILE* f = std::fopen(tmp.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    bool ok = true;
+    for (uint32_t a = 0; a < g.n && ok; ++a)
+        for (uint32_t e = g.row_ptr[a]; e < g.row_ptr[a + 1] && ok; ++e) {
+            bool any = false;
+            for (size_t j = 0; j < slices; ++j) any = any || loads[j * g.m + e] != 0;
+            if (!any) continue;
+            ok = std::fprintf(f, "%u %u %u", e, a, g.dst[e]) > 0;
+            for (size_t j = 0; j < slices && ok; ++j)
+                ok = std::fprintf(f, " %llu", (unsigned long long)loads[j * g.m + e]) > 0;
+            ok = ok && std::fputc('\n', f) != EOF;
+        }
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
+        ::unlink(tmp.c_str());
+        throw std::runtime_error("cannot write " + path);
+    }
+}
+
 static bool write_answer(const std::string& path, const std::string& line) {
     // process_query.send_remote mkfifo's the answer before writing the request
     // (process_query.py:72-73); tolerate a late mkfifo for up to 10 s
@@ -246,7 +283,13 @@ int main(int argc, char** argv) {
                      "                  (with --slice-moves S one cost: move h under diff "
                      "min(h / S, last));\n"
                      "                  \"debug\": true in a request adds nothing: .res is the "
-                     "costs file\n");
+                     "costs file\n"
+                     "       [--loads [--load-slices K --load-slice-moves S]]  table-search only: "
+                     "answer through\n"
+                     "                  cpd_query_loads (demand 1 per query) and write every "
+                     "loaded edge to\n"
+                     "                  <query file>.loads: edge from to load_0 ... load_{K-1}\n"
+                     "                  (K slices: move h counts in slice min(h / S, K - 1))\n");
         return 2;
     }
     // table-search (make_fifos.py:20) or the CPD-heuristic search
@@ -279,6 +322,21 @@ int main(int argc, char** argv) {
     const long long slice_moves = a.num("slice-moves", 0);
     if ((slice_moves && !costs) || slice_moves < 0 || slice_moves > 0xFFFFFFFFll) {
         std::fprintf(stderr, "fifo_auto: --slice-moves S needs --costs and 0 <= S < 2^32\n");
+        return 2;
+    }
+    const bool loads = a.has("loads");
+    if (loads && (search || paths || costs)) {
+        std::fprintf(stderr, "fifo_auto: --loads needs --alg table-search without --paths or "
+                             "--costs (a cpd-search's route is not the walk's; --paths and --costs "
+                             "answer through cpd_query_paths and cpd_query_costs)\n");
+        return 2;
+    }
+    const long long load_slices = a.num("load-slices", 1), load_slice_moves = a.num("load-slice-moves", 0);
+    if (((a.has("load-slices") || a.has("load-slice-moves")) && !loads) || load_slices < 1 ||
+        load_slices > (long long)CPD_MAX_LOAD_SLICES || load_slice_moves < 0 ||
+        load_slice_moves > 0xFFFFFFFFll || (load_slices == 1) != (load_slice_moves == 0)) {
+        std::fprintf(stderr, "fifo_auto: --load-slices K --load-slice-moves S need --loads, 2 <= K "
+                             "<= %u and 0 < S < 2^32 (both or neither)\n", CPD_MAX_LOAD_SLICES);
         return 2;
     }
     int mcode = cli::method_code(method);
@@ -606,6 +664,11 @@ int main(int argc, char** argv) {
                 rc = cpd_query_costs(ix, k_moves, (uint32_t)slice_moves, &st);
                 if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
                 write_costs(ix, qfile, s, t, slice_moves ? 1u : active_nsets);
+            } else if (loads) {
+                rc = cpd_query_loads(ix, k_moves, nullptr, (uint32_t)load_slices,
+                                     (uint32_t)load_slice_moves, 0, &st);
+                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                write_loads(ix, qfile, g, (size_t)load_slices);
             } else if (paths) {
                 static std::vector<uint64_t> poff;
                 poff.resize(nq + 1);

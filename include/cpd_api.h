@@ -458,6 +458,57 @@ int  cpd_query_paths_fetch(cpd_index* ix, uint32_t first, uint32_t count, uint32
 int  cpd_index_set_weight_sets(cpd_index* ix, uint32_t nsets, const uint32_t* const* w);
 int  cpd_query_costs(cpd_index* ix, int32_t k_moves, uint32_t slice_moves, cpd_query_stats* st);
 int  cpd_query_costs_fetch(cpd_index* ix, uint64_t* costs, uint32_t* hops, uint8_t* finished);
+
+/* Edge loads — how much demand every edge carries when a batch of queries is
+ * routed: the quantity a congestion diff is made from (the reference takes
+ * its `diffs` as given, process_query.py:178; nothing in it produces them).
+ * cpd_query_loads: on the queries of the last cpd_query_prepare, the walk of
+ * cpd_query_run (k_moves with its meaning, the n-move loop guard, and the
+ * k_moves = 0 refill limit described at cpd_query_paths).  For every move a
+ * walk takes, demand[q] (nq values in the CALLER's query order; NULL = 1 for
+ * every query) is added to the counter of (slice j, edge e):
+ *   e  the original index of the out-edge taken — its position in the .xy
+ *      file order, the index cpd_index_set_weights uses (parallel edges are
+ *      told apart);
+ *   j  min(h / slice_moves, nslices - 1) for move number h of the walk
+ *      (0-based); j = 0 when nslices == 1.  The load per congestion state of
+ *      a trip replanned every slice_moves moves, the counterpart of
+ *      cpd_query_costs' sliced mode.
+ * A move that names no out-edge ends the walk and adds nothing; a walk that
+ * stops unfinished (k_moves, the loop guard) has loaded the moves it took.
+ * Counters are 64-bit: a demand of 0xFFFFFFFF on every query never wraps.
+ * Integer adds commute, so the table is exact and the same in every run; it
+ * never depends on the weights.
+ * flags = 0: the table is zeroed first.  CPD_LOADS_ACCUMULATE: the call adds
+ * to what earlier calls on this index left (nothing: it starts from zero),
+ * across cpd_query_prepare calls — a demand set larger than a batch goes
+ * through in pieces, and workers' tables add up on the head; CPD_E_ARG when
+ * nslices or slice_moves differ from the resident table's.
+ * Also does what cpd_query_run does (st, and cpd_query_fetch afterwards
+ * returns this walk's cost / hops / finished under the index's current
+ * weights) and, like it, ends the validity of fetched paths.
+ * CPD_E_ARG when nslices is 0 or above CPD_MAX_LOAD_SLICES, slice_moves is 0
+ * with nslices > 1 or non-zero with nslices == 1, or the index is incomplete.
+ * cpd_query_loads_fetch: loads[j * m + e], nslices * m values, permuted from
+ * the table's adjacency-slot order to original edge order on the GPU and
+ * copied out once.  CPD_E_ARG before any cpd_query_loads on the index, or
+ * after a clear.
+ * The table (8 B per slice and adjacency slot: n x 1, 2, 4, 8 or 16 slots
+ * by the graph's largest out-degree) lives in HBM until cpd_query_loads_clear
+ * or cpd_index_free.  cpd_index_set_weights, the weight sets,
+ * cpd_query_paths, cpd_query_costs and cpd_query_search neither see nor
+ * change it.  When a device arena is committed the table is carved from it;
+ * the arena never takes a buffer back, so a table larger than any before it
+ * on this index (or one made again after a clear) uses up that many more
+ * arena bytes until cpd_device_arena_release (what does not fit is allocated
+ * separately).                                                              */
+#define CPD_MAX_LOAD_SLICES 8u
+#define CPD_LOADS_ACCUMULATE 1u
+int  cpd_query_loads(cpd_index* ix, int32_t k_moves, const uint32_t* demand /* nq, caller order; NULL = 1 each */,
+                     uint32_t nslices /* 1..8 */, uint32_t slice_moves /* 0 iff nslices == 1 */,
+                     uint32_t flags, cpd_query_stats* st);
+int  cpd_query_loads_fetch(cpd_index* ix, uint64_t* loads /* nslices * m */);
+int  cpd_query_loads_clear(cpd_index* ix);
 void cpd_index_free(cpd_index* ix);
 
 /* [gpu] CPD-heuristic search — fifo_auto's other algorithm family
