@@ -37,6 +37,7 @@ FM_ALL = 0xFFFF
 MAX_WEIGHT_SETS = 8
 MAX_LOAD_SLICES = 8
 LOADS_ACCUMULATE = 1
+TIMED_LOADS = 2
 
 EXPORTED = [
     "cpd_last_error", "cpd_version", "cpd_partition", "cpd_partition_nbuckets",
@@ -60,6 +61,7 @@ EXPORTED = [
     "cpd_query_paths", "cpd_query_paths_fetch", "cpd_query_search_paths",
     "cpd_index_set_weight_sets", "cpd_query_costs", "cpd_query_costs_fetch",
     "cpd_query_loads", "cpd_query_loads_fetch", "cpd_query_loads_clear",
+    "cpd_query_timed", "cpd_query_timed_fetch",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
@@ -551,6 +553,7 @@ class Index:
         self._nq, self._path_offsets = 0, None  # prepared queries; offsets of their paths
         self._nsets, self._cost_cols = 0, None  # weight sets loaded; columns of the last costs_run
         self._load_slices = None                # slices of the resident load table
+        self._timed = False                     # a timed_run on the prepared queries
         self._h = C.c_void_p()
         if _handle is not None:
             self._h = _handle
@@ -620,6 +623,7 @@ class Index:
         nq = len(s)
         self._nq, self._path_offsets = 0, None  # cpd_query_batch prepares and runs
         self._cost_cols = None
+        self._timed = False
         cost = np.empty(nq, np.uint64)
         hops = np.empty(nq, np.uint32)
         fin = np.empty(nq, np.uint8)
@@ -634,6 +638,7 @@ class Index:
         s, t = _u32(s), _u32(t)
         self._nq, self._path_offsets = 0, None  # the library drops the last batch's paths
         self._cost_cols = None                  # ... and its costs
+        self._timed = False                     # ... and its timed results
         _check(lib.cpd_query_prepare(self._h, _ptr(s, u32p), _ptr(t, u32p), C.c_uint32(len(s))))
         self._nq = len(s)
 
@@ -780,6 +785,61 @@ class Index:
         """Drop the resident load table (cpd_query_loads_clear)."""
         _check(lib.cpd_query_loads_clear(self._h))
         self._load_slices = None
+
+    def timed(self, s, t, depart=None, period=None, demand=None, k_moves: int = -1,
+              loads: bool = False, accumulate: bool = False):
+        """The table-search walks of (s, t) on a clock (cpd_query_timed):
+        (cost, hops, finished, stats).  Query q leaves at depart[q] (u64,
+        weight units; None = 0 each); a move whose edge is entered at clock
+        time tau is costed under weight set min(tau // period, nsets - 1) and
+        advances the clock by that weight; cost = arrival - departure.
+        loads=True: demand[q] (u32; None = 1 each) is added to counter (set,
+        edge) of the load table for every move — loads_fetch() returns its
+        nsets planes; accumulate=True adds to a resident timed table of the
+        same sets and period."""
+        self.prepare(s, t)
+        st = self.timed_run(depart, period, demand, k_moves, loads, accumulate)
+        cost, hops, fin = self.timed_fetch()
+        return cost, hops, fin, st
+
+    def timed_run(self, depart=None, period=None, demand=None, k_moves: int = -1,
+                  loads: bool = False, accumulate: bool = False) -> dict:
+        """cpd_query_timed on the prepared queries: stats."""
+        if period is None:
+            raise ValueError("period is required")
+        self._timed = False
+        dp = d = None
+        if depart is not None:
+            dp = np.ascontiguousarray(depart, dtype=np.uint64)
+            if dp.shape != (self._nq,):
+                raise ValueError("depart must have one entry per prepared query")
+        if demand is not None:
+            d = _u32(demand)
+            if d.shape != (self._nq,):
+                raise ValueError("demand must have one entry per prepared query")
+        flags = (TIMED_LOADS if loads else 0) | (LOADS_ACCUMULATE if accumulate else 0)
+        st = QueryStats()
+        _check(lib.cpd_query_timed(self._h, C.c_int32(k_moves), _ptr(dp, u64p),
+                                   C.c_uint64(period), _ptr(d, u32p), C.c_uint32(flags),
+                                   C.byref(st)))
+        self._timed = True
+        if loads:
+            self._load_slices = self._nsets
+        return {k: getattr(st, k) for k, _ in QueryStats._fields_}
+
+    def timed_fetch(self):
+        """(cost u64[nq], hops, finished) of the last timed_run() in the
+        caller's order (cpd_query_timed_fetch)."""
+        if not self._timed:
+            raise CpdError(CPD_E_ARG, "timed fetch: no timed() / timed_run() on the prepared "
+                                      "queries yet")
+        nq = self._nq
+        cost = np.empty(nq, np.uint64)
+        hops = np.empty(nq, np.uint32)
+        fin = np.empty(nq, np.uint8)
+        _check(lib.cpd_query_timed_fetch(self._h, _ptr(cost, u64p), _ptr(hops, u32p),
+                                         _ptr(fin, u8p)))
+        return cost, hops, fin
 
     def search(self, s, t, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
                capacity=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,

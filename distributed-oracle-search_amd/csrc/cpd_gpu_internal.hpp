@@ -507,12 +507,24 @@ struct cpd_index {
     // ld_slices planes of n << adj_shift u64 counters, counter (column <<
     // adj_shift) + move — kept across prepares until cpd_query_loads_clear;
     // ld_slice_moves: the moves per slice it was filled with (0: one plane);
-    // the batch's demand (caller order) and the fetch's edge-order copy.  The
+    // ld_period: non-zero for a table cpd_query_timed filled — its planes are
+    // the intervals [j * ld_period, (j + 1) * ld_period) of clock time, the
+    // last open-ended, ld_slices = the sets it was filled under, ld_slice_moves
+    // = 0; a table is of one kind, accumulated into only by its own.
+    // The batch's demand (caller order) and the fetch's edge-order copy.  The
     // table is carved from the arena when one is committed (see wsets above).
     DevBuf<uint64_t> ld_tab, ld_out;
     DevBuf<uint32_t> ld_demand;
     uint32_t ld_slices = 0, ld_slice_moves = 0;
+    uint64_t ld_period = 0;
     bool loads_ready = false;
+    // timed walks (cpd_query_timed): the batch's departures (caller order)
+    // and the result buffers of the last call in sorted order; timed_ready:
+    // they are those of the prepared queries.  Carved like cs_cost.
+    DevBuf<uint64_t> tm_depart, tm_cost;
+    DevBuf<uint32_t> tm_hops;
+    DevBuf<uint8_t> tm_fin;
+    bool timed_ready = false;
     // search paths (cpd_query_search_paths), scratch of one call, freed when
     // it returns (the cursor stays): the prefix pool and its cursor;
     // per query (sorted order) the prefix's place and length, v* and lw(v*);

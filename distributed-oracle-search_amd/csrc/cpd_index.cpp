@@ -451,6 +451,7 @@ int cpd_query_prepare(cpd_index* ix, const uint32_t* s, const uint32_t* t, uint3
         ix->searched = false;
         ix->paths_ready = false;
         ix->costs_ready = false;
+        ix->timed_ready = false;
         const size_t m = std::max<uint32_t>(nq, 1u);
         for (DevBuf<uint32_t>* b : {&ix->qin_s, &ix->qin_t, &ix->qkey, &ix->qkey2, &ix->qval,
                                     &ix->qperm, &ix->qs, &ix->qt, &ix->qrow, &ix->hops})
@@ -557,6 +558,20 @@ double run_walk(cpd_index* ix, int32_t k_moves, cpd_query_stats* st) {
         st->kernel_ms = ms;
     }
     return bytes;
+}
+
+// The load table's fetch order (edge loads, timed walks; at first use):
+// column-space edge ec of column c sits in slot c * stride + its place in c's
+// out-list; edge_perm names its file edge.
+void ensure_slot_of_edge(cpd_graph* g) {
+    if (g->slot_of_edge_d.p) return;
+    const size_t stride = (size_t)1 << g->adj_shift;
+    std::vector<uint32_t> soe(g->m);
+    for (uint32_t c = 0; c < g->n; ++c)
+        for (uint32_t e = g->rowc_host[c]; e < g->rowc_host[c + 1]; ++e)
+            soe[g->edge_perm[e]] = (uint32_t)(c * stride + (e - g->rowc_host[c]));
+    g->slot_of_edge_d.upload(soe.data(), soe.size(), g->stream);
+    HIP_CHECK(hipStreamSynchronize(g->stream));  // soe leaves scope
 }
 
 }  // namespace
@@ -869,6 +884,9 @@ int cpd_query_loads(cpd_index* ix, int32_t k_moves, const uint32_t* demand, uint
                     "loads: index incomplete (" + std::to_string(ix->added) + " of " +
                         std::to_string(ix->nrows) + " rows appended)");
         const bool keep = (flags & CPD_LOADS_ACCUMULATE) && ix->loads_ready;
+        CPD_REQUIRE(!keep || !ix->ld_period, CPD_E_ARG,
+                    "loads: accumulate into the table of a timed walk (period " +
+                        std::to_string(ix->ld_period) + ")");
         CPD_REQUIRE(!keep || (ix->ld_slices == nslices && ix->ld_slice_moves == slice_moves),
                     CPD_E_ARG,
                     "loads: accumulate into a table of " + std::to_string(ix->ld_slices) +
@@ -885,16 +903,7 @@ int cpd_query_loads(cpd_index* ix, int32_t k_moves, const uint32_t* demand, uint
         ix->paths_ready = false;
         const bool dense = ix->use_dense();
         if (dense && !ix->dense_ready) ensure_dense(ix);
-        if (!g->slot_of_edge_d.p) {
-            // column-space edge ec of column c sits in slot c * stride + its
-            // place in c's out-list; edge_perm names its file edge
-            std::vector<uint32_t> soe(g->m);
-            for (uint32_t c = 0; c < g->n; ++c)
-                for (uint32_t e = g->rowc_host[c]; e < g->rowc_host[c + 1]; ++e)
-                    soe[g->edge_perm[e]] = (uint32_t)(c * stride + (e - g->rowc_host[c]));
-            g->slot_of_edge_d.upload(soe.data(), soe.size(), s);
-            HIP_CHECK(hipStreamSynchronize(s));  // soe leaves scope
-        }
+        ensure_slot_of_edge(g);
         if (!keep) {
             ix->loads_ready = false;
             {
@@ -904,6 +913,7 @@ int cpd_query_loads(cpd_index* ix, int32_t k_moves, const uint32_t* demand, uint
             HIP_CHECK(hipMemsetAsync(ix->ld_tab.p, 0, (size_t)nslices * nslots * sizeof(uint64_t), s));
             ix->ld_slices = nslices;
             ix->ld_slice_moves = slice_moves;
+            ix->ld_period = 0;
             ix->loads_ready = true;
         }
         if (demand && nq) ix->ld_demand.upload(demand, nq, s);
@@ -980,7 +990,153 @@ int cpd_query_loads_clear(cpd_index* ix) {
         ix->ld_tab.release();
         ix->ld_out.release();
         ix->ld_slices = ix->ld_slice_moves = 0;
+        ix->ld_period = 0;
         ix->loads_ready = false;
+    });
+}
+
+int cpd_query_timed(cpd_index* ix, int32_t k_moves, const uint64_t* depart, uint64_t period,
+                    const uint32_t* demand, uint32_t flags, cpd_query_stats* st) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        CPD_REQUIRE(ix->nsets, CPD_E_ARG, "timed: no weight sets loaded (cpd_index_set_weight_sets)");
+        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
+                    "timed: index incomplete (" + std::to_string(ix->added) + " of " +
+                        std::to_string(ix->nrows) + " rows appended)");
+        const bool loads = (flags & CPD_TIMED_LOADS) != 0;
+        CPD_REQUIRE(loads || !(flags & CPD_LOADS_ACCUMULATE), CPD_E_ARG,
+                    "timed: CPD_LOADS_ACCUMULATE without CPD_TIMED_LOADS");
+        CPD_REQUIRE(period >= 1 && period <= (1ull << 60), CPD_E_ARG,
+                    "timed: period " + std::to_string(period) + ", 1 to 2^60");
+        const uint32_t nq = ix->nq;
+        if (depart)
+            for (uint32_t q = 0; q < nq; ++q)
+                CPD_REQUIRE(depart[q] < (1ull << 63), CPD_E_ARG,
+                            "timed: departure " + std::to_string(depart[q]) + " of query " +
+                                std::to_string(q) + ", must be below 2^63");
+        const uint32_t nsets = ix->nsets;
+        const bool keep = loads && (flags & CPD_LOADS_ACCUMULATE) && ix->loads_ready;
+        CPD_REQUIRE(!keep || (ix->ld_period == period && ix->ld_slices == nsets), CPD_E_ARG,
+                    "timed: accumulate into a table of " + std::to_string(ix->ld_slices) +
+                        " planes of " +
+                        (ix->ld_period ? "period " + std::to_string(ix->ld_period)
+                                       : std::to_string(ix->ld_slice_moves) + " moves") +
+                        " asked with " + std::to_string(nsets) + " sets of period " +
+                        std::to_string(period));
+        cpd_graph* g = ix->g;
+        g->select();
+        hipStream_t s = g->stream;
+        const size_t stride = (size_t)1 << g->adj_shift;
+        // the kernel keeps a slot as u32, 0xFFFFFFFF = none
+        CPD_REQUIRE(!loads || stride * g->n < 0xFFFFFFFFull, CPD_E_RANGE,
+                    "timed: 2^32 adjacency slots or more");
+        const uint32_t nslots = g->n << g->adj_shift;
+        ix->timed_ready = false;
+        const bool dense = ix->use_dense();
+        if (dense && !ix->dense_ready) ensure_dense(ix);
+        {
+            ArenaScope carve;
+            const size_t m = std::max<uint32_t>(nq, 1u);
+            ix->tm_cost.alloc(m);
+            ix->tm_hops.alloc(m);
+            ix->tm_fin.alloc(m);
+        }
+        if (loads) {
+            ensure_slot_of_edge(g);
+            if (!keep) {
+                ix->loads_ready = false;
+                {
+                    ArenaScope carve;
+                    ix->ld_tab.alloc((size_t)nsets * nslots);
+                }
+                HIP_CHECK(hipMemsetAsync(ix->ld_tab.p, 0, (size_t)nsets * nslots * sizeof(uint64_t), s));
+                ix->ld_slices = nsets;
+                ix->ld_slice_moves = 0;
+                ix->ld_period = period;
+                ix->loads_ready = true;
+            }
+        }
+        if (depart && nq) ix->tm_depart.upload(depart, nq, s);
+        const uint64_t* dep = depart && nq ? ix->tm_depart.p : nullptr;
+        if (loads && demand && nq) ix->ld_demand.upload(demand, nq, s);
+        const uint32_t* dem = loads && demand && nq ? ix->ld_demand.p : nullptr;
+        HIP_CHECK(hipMemsetAsync(ix->agg.p, 0, 3 * sizeof(unsigned long long), s));
+        Events<2> ev(g);
+        const hipEvent_t a = ev.e[0], b = ev.e[1];
+        HIP_CHECK(hipEventRecord(a, s));
+        (void)hipGetLastError();
+        uint64_t* tab = loads ? ix->ld_tab.p : nullptr;
+        // the route needs the adjacency's heads only: the free-flow one serves
+        if (nq && dense)
+            launch_table_timed_dense(g->adj.p, g->adj_shift, ix->dense.p, g->npad, g->tlb,
+                                     ix->wsets.p, nsets, ix->qs.p, ix->qt.p, ix->qrow.p,
+                                     ix->qperm.p, dep, period, dem, nq, k_moves, g->n, tab,
+                                     ix->tm_cost.p, ix->tm_hops.p, ix->tm_fin.p, ix->agg.p, s);
+        else if (nq)
+            launch_table_timed(g->adj.p, g->adj_shift, ix->off.p, ix->runs.p, ix->wsets.p, nsets,
+                               ix->qs.p, ix->qt.p, ix->qrow.p, ix->qperm.p, dep, period, dem, nq,
+                               k_moves, g->n, tab, ix->tm_cost.p, ix->tm_hops.p, ix->tm_fin.p,
+                               ix->agg.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(b, s));
+        unsigned long long hagg[3] = {0, 0, 0};  // finished, moves, cost (wave_stats)
+        HIP_CHECK(hipMemcpyAsync(hagg, ix->agg.p, sizeof hagg, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+        if (g->timing) {
+            // the walk's bytes + a record per move (+ one 8-B counter with
+            // loads) + the permutation word and what is read through it per
+            // query + the stored cost
+            Agg& ag = g->agg[dense ? "table_timed_dense" : "table_timed"];
+            ag.launches++;
+            ag.ms += ms;
+            const double per_q = (dep ? 8.0 : 0.0) + (dem ? 4.0 : 0.0);
+            ag.bytes += walk_model_bytes(ix, dense, nq, hagg[1]) +
+                        (4.0 * ix->wset_words + (loads ? 8.0 : 0.0)) * (double)hagg[1] +
+                        (per_q + 4.0) * nq + 8.0 * nq;
+        }
+        if (st) {
+            st->queries = nq;
+            st->finished = hagg[0];
+            st->hops = hagg[1];
+            st->cost = hagg[2];
+            st->kernel_ms = ms;
+        }
+        ix->timed_ready = true;
+    });
+}
+
+int cpd_query_timed_fetch(cpd_index* ix, uint64_t* cost, uint32_t* hops, uint8_t* finished) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "null index");
+        CPD_REQUIRE(ix->timed_ready, CPD_E_ARG,
+                    "timed fetch: no cpd_query_timed on the prepared queries yet");
+        cpd_graph* g = ix->g;
+        g->select();
+        const uint32_t nq = ix->nq;
+        if (!nq) return;
+        // sorted order -> the caller's, on the GPU, then copied out
+        hipStream_t st = g->stream;
+        ix->qout.alloc((size_t)nq * 8u);
+        if (cost) {
+            launch_scatter_u64(ix->tm_cost.p, ix->qperm.p, nq,
+                               reinterpret_cast<uint64_t*>(ix->qout.p), st);
+            HIP_CHECK(hipMemcpyAsync(cost, ix->qout.p, nq * 8ull, hipMemcpyDeviceToHost, st));
+        }
+        if (hops) {
+            HIP_CHECK(hipStreamSynchronize(st));  // qout is reused
+            launch_scatter_u32(ix->tm_hops.p, ix->qperm.p, nq, 1u,
+                               reinterpret_cast<uint32_t*>(ix->qout.p), st);
+            HIP_CHECK(hipMemcpyAsync(hops, ix->qout.p, nq * 4ull, hipMemcpyDeviceToHost, st));
+        }
+        if (finished) {
+            HIP_CHECK(hipStreamSynchronize(st));
+            launch_scatter_u8(ix->tm_fin.p, ix->qperm.p, nq, ix->qout.p, st);
+            HIP_CHECK(hipMemcpyAsync(finished, ix->qout.p, nq, hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
     });
 }
 

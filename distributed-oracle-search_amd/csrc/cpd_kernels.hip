@@ -3567,6 +3567,230 @@ __global__ __launch_bounds__(256) void loads_gather(const unsigned long long* __
     out[i] = tab[(size_t)j * nslots + slot_of_edge[e]];
 }
 
+// Timed walks (cpd_query_timed): table_walk's walk once, every move costed —
+// and, with LOADS, counted — under the weight set of the CLOCK TIME at which
+// its edge is entered.  A lane carries a u64 clock tau, started at its query's
+// departure; move h on edge e_h takes c_h = W_j[e_h], j = min(tau / period,
+// nsets - 1), and advances the clock by c_h (the weight is frozen when the
+// edge is entered).  Stored per query: tau_end - departure, hops, finished.
+// The frame (a wave owns a chunk, lanes are refilled), the retire condition
+// and walk_begin / walk_move are table_walk's, so hops, finished and the route
+// are the plain walk's; wsets / zrec are costs_walk's records, tab is
+// loads_walk's table with one plane per set.
+// The set of move h depends on the sum so far, which costs_walk's and
+// loads_walk's do not: loading only word j_h of the record would be a second
+// dependent round trip per hop.  So the WHOLE record is loaded when the move
+// is known (its address needs nothing else; into pend, every lane, a lane
+// without a move the zero record — costs_walk's one definition) and its word
+// is chosen in registers ONE ITERATION LATER, after that iteration's own loads
+// (adjacency row, move word or first run probe; wide adjacency: the edge) are
+// issued — a compare / select chain over the KW registers (indexing them by
+// the per-lane j would send the record to scratch).  That place is also where
+// the plane of the move is known, so the add of LOADS (loads_walk's: guarded,
+// no-return, relaxed, agent scope, 8 B; prec = the record's index is the
+// counter's slot, zrec = no move) and the clock update share it.
+// No division in the loop: a lane keeps j and bound = (j + 1) * period and,
+// after adding a weight, steps j while the clock has reached bound (one heavy
+// edge can cross several periods; at most nsets - 1 steps per walk in all).
+// bound <= nsets * period <= 2^63 and tau < 2^63 + n * 2^32: nothing wraps.
+// A lane that retires settles its pending record where it stands — word, add
+// and clock — before it stores, then starts the next query's clock at its
+// departure MINUS the word the common place will choose from the record still
+// in pend (u64 wraps; costs_walk's restart), and prec = zrec: nothing is added
+// twice, and nothing is left pending when the chunk runs dry (every lane has
+// retired).  Departure and demand are in the caller's order: read through
+// qperm, once per query.
+// Word `set` of a record held in registers: a compare / select chain.  The
+// words come by value: written over the record where it lives (an array, or
+// vectors a lambda captures), hipcc folds the chain into one indexed read and
+// moves the record to LDS for it (4 or 8 KiB per workgroup, seen in the
+// kernel's resource usage).
+template <int KW>
+__device__ __forceinline__ uint32_t timed_word(uint32_t set, uint32_t w0, uint32_t w1, uint32_t w2,
+                                               uint32_t w3, uint32_t w4, uint32_t w5, uint32_t w6,
+                                               uint32_t w7) {
+    uint32_t c = w0;
+    c = set == 1u ? w1 : c;
+    c = set == 2u ? w2 : c;
+    c = set == 3u ? w3 : c;
+    if constexpr (KW == 8) {
+        c = set == 4u ? w4 : c;
+        c = set == 5u ? w5 : c;
+        c = set == 6u ? w6 : c;
+        c = set == 7u ? w7 : c;
+    }
+    return c;
+}
+
+template <int SHIFT, int KW, bool LOADS, class Rows>
+__device__ __forceinline__ void timed_walk(
+    const uint2* __restrict__ adj, Rows rows, const uint32_t* __restrict__ wsets, uint32_t zrec,
+    const uint32_t* __restrict__ qs, const uint32_t* __restrict__ qt,
+    const uint32_t* __restrict__ qrow, const uint32_t* __restrict__ qperm,
+    const uint64_t* __restrict__ depart, const uint32_t* __restrict__ demand, uint32_t nq,
+    uint32_t chunk, uint32_t limit, uint32_t nsets, uint64_t period, uint32_t nslots,
+    unsigned long long* __restrict__ tab, uint64_t* __restrict__ cost_out,
+    uint32_t* __restrict__ hops_out, uint8_t* __restrict__ fin_out,
+    unsigned long long* __restrict__ agg) {
+    static_assert(KW == 4 || KW == 8, "records are one or two 16-B loads");
+    constexpr bool kDense = std::is_same<Rows, DenseRows>::value;
+    constexpr int NQ = SHIFT == 2 ? 2 : 1;  // 16-B pieces of an adjacency row
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t q0l = wave * chunk;
+    const uint32_t q0 = q0l < nq ? (uint32_t)q0l : nq;
+    const uint32_t q1 = (uint32_t)min((uint64_t)nq, q0l + chunk);
+    uint64_t sum_cost = 0;
+    uint32_t sum_hops = 0, sum_fin = 0;
+    uint64_t tau = 0, dep = 0;   // the clock, the pending record excluded; the departure
+    uint64_t bound = period;     // (j + 1) * period
+    uint32_t j = 0;              // the set of the clock: min(tau / period, nsets - 1)
+    uint32_t dem = 0;            // the demand of the lane's query
+    // the record of the last iteration's move (KW 4: pend1 unused)
+    uint4 pend0 = make_uint4(0u, 0u, 0u, 0u), pend1 = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t prec = zrec;        // its index (= the counter's slot); zrec: no move
+    WalkState w;
+    uint32_t next = q0;  // wave-uniform: first query of the chunk not yet started
+    w.q = kIdleQ;        // idle: column 0 of row 0 stays loadable
+    w.cur = 0;
+    w.t = 0;
+    w.hops = 0;
+    w.bad = false;
+    w.cost = 0;
+    w.pos = 0;
+    w.R = 0;
+    w.row = rows_base(rows);
+    auto word_of = [&](uint32_t set) {  // the pending record's weight in a set
+        return timed_word<KW>(set, pend0.x, pend0.y, pend0.z, pend0.w, pend1.x, pend1.y, pend1.z,
+                              pend1.w);
+    };
+    auto advance = [&]() {  // j, bound follow the clock
+        while (j + 1u < nsets && tau >= bound) {
+            ++j;
+            bound += period;
+        }
+    };
+    // the pending move: its word under the clock's set, its add, the clock
+    auto settle_move = [&]() {
+        const uint32_t c = word_of(j);
+        if constexpr (LOADS) loads_add(tab, nslots, prec == zrec ? kNoSlot : prec, j, dem);
+        tau += c;
+        advance();
+    };
+    auto begin = [&](uint32_t q) {
+        walk_begin(w, q, qs, qt, qrow, rows);
+        const uint32_t qo = qperm[q];
+        dep = depart ? depart[qo] : 0ull;
+        if constexpr (LOADS) dem = demand ? demand[qo] : 1u;
+        // the walk's state is in registers, no load of it pending (costs_walk's settle)
+        if constexpr (kDense)
+            asm volatile("" ::"v"(w.cur), "v"(w.t), "v"(w.row), "v"(dep), "v"(dem));
+        else
+            asm volatile("" ::"v"(w.cur), "v"(w.t), "v"(w.row), "v"(w.R), "v"(dep), "v"(dem));
+        j = 0;
+        bound = period;
+        tau = dep;
+        advance();
+        tau = dep - word_of(j);  // + that word at the common place: the departure
+    };
+    if (next + lane < q1) begin(next + lane);
+    next = min(q1, next + 64u);
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    for (;;) {
+        // retire finished walks; their lanes take the next queries of the chunk
+        const bool idle = w.q == kIdleQ;
+        const bool done = !idle && (w.cur == w.t || w.hops >= limit || w.bad);
+        const uint64_t m = __ballot(done);
+        if (m) {
+            if (done) {
+                const uint32_t fin = w.cur == w.t ? 1u : 0u;
+                settle_move();  // the walk's last move
+                prec = zrec;
+                const uint64_t cost = tau - dep;
+                cost_out[w.q] = cost;
+                hops_out[w.q] = w.hops;
+                fin_out[w.q] = (uint8_t)fin;
+                sum_cost += cost;
+                sum_hops += w.hops;
+                sum_fin += fin;
+                const uint32_t nqi = next + (uint32_t)__builtin_popcountll(m & lt_mask);
+                if (nqi < q1) begin(nqi);
+                else w.q = kIdleQ;
+            }
+            next = min(q1, next + (uint32_t)__builtin_popcountll(m));
+        }
+        if (!__any(w.q != kIdleQ)) break;
+        // this hop's loads that depend on cur alone, for every lane (an idle
+        // or arrived lane stands on a valid column of a valid row)
+        uint4 p[NQ];
+        uint32_t word;
+        if (SHIFT == 0) {
+            const uint2 e = adj[w.cur];
+            p[0] = make_uint4(e.x, e.y, kNoEdge, 0u);
+        } else if (SHIFT <= 2) {
+            const uint4* a4 = reinterpret_cast<const uint4*>(adj) + (size_t)w.cur * NQ;
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) p[k] = a4[k];
+        }
+        if constexpr (kDense) word = w.row[w.cur >> (5u - rows.tb.lb)];
+        else word = w.row[w.pos];  // the run search's first probe
+        // the last iteration's move, behind them; pinned before the next record's loads
+        auto settle_behind = [&]() {
+            __builtin_amdgcn_sched_barrier(0);
+            settle_move();
+            asm volatile("" : "+v"(tau), "+v"(bound), "+v"(j));
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        if (SHIFT <= 2) settle_behind();
+        const bool walking = w.q != kIdleQ && w.cur != w.t;
+        uint32_t mv;
+        if constexpr (kDense) {
+            const uint32_t cm = 31u >> rows.tb.lb, mm = (1u << (1u << rows.tb.lb)) - 1u;
+            mv = (word >> ((w.cur & cm) << rows.tb.lb)) & mm;
+        } else {
+            mv = word & 0xFu;
+            if (walking) mv = walk_move(w, rows);
+        }
+        const bool slot_ok = (mv >> SHIFT) == 0u;  // else: names no slot of cur, malformed row
+        const uint32_t slot = mv & ((1u << SHIFT) - 1u);
+        uint32_t ex;
+        if (SHIFT <= 2) {
+            const uint4 e = (NQ == 2 && (slot & 2u)) ? p[NQ - 1] : p[0];
+            ex = (slot & 1u) ? e.z : e.x;
+        } else {  // wide adjacency: the edge load follows the move, the pending move follows it
+            const uint2 e = adj[((size_t)w.cur << SHIFT) + slot];
+            settle_behind();
+            ex = e.x;
+        }
+        const bool step = walking && slot_ok && ex != kNoEdge;
+        w.bad = w.bad || (walking && !step);
+        prec = step ? (w.cur << SHIFT) + slot : zrec;
+        const uint4* __restrict__ r4 = reinterpret_cast<const uint4*>(wsets) + (size_t)prec * (KW / 4);
+        pend0 = r4[0];
+        if constexpr (KW == 8) pend1 = r4[1];
+        if (step) {
+            w.cur = ex;
+            ++w.hops;
+        }
+    }
+    wave_stats(sum_cost, sum_hops, sum_fin, agg);
+}
+
+template <int SHIFT, int KW, bool LOADS, class Rows>
+__global__ __launch_bounds__(256) void table_walk_timed(
+    const uint2* __restrict__ adj, Rows rows, const uint32_t* __restrict__ wsets, uint32_t zrec,
+    const uint32_t* __restrict__ qs, const uint32_t* __restrict__ qt,
+    const uint32_t* __restrict__ qrow, const uint32_t* __restrict__ qperm,
+    const uint64_t* __restrict__ depart, const uint32_t* __restrict__ demand, uint32_t nq,
+    uint32_t chunk, uint32_t limit, uint32_t nsets, uint64_t period, uint32_t nslots,
+    unsigned long long* __restrict__ tab, uint64_t* __restrict__ cost_out,
+    uint32_t* __restrict__ hops_out, uint8_t* __restrict__ fin_out,
+    unsigned long long* __restrict__ agg) {
+    timed_walk<SHIFT, KW, LOADS>(adj, rows, wsets, zrec, qs, qt, qrow, qperm, depart, demand, nq,
+                                 chunk, limit, nsets, period, nslots, tab, cost_out, hops_out,
+                                 fin_out, agg);
+}
+
 __device__ void wave_stats(uint64_t cost, uint32_t hops, uint32_t fin,
                            unsigned long long* __restrict__ agg) {
     // wave reduction, one atomic per wave per counter
@@ -5295,6 +5519,73 @@ void launch_table_loads(const uint32_t* adj, uint32_t shift, const uint64_t* off
     launch_walk_loads(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs}, qs,
                       qt, qrow, qperm, demand, nq, n, walk_limit(kmoves, n), nslices, slice, tab,
                       cost, hops, fin, agg, kRleWaves, 1u << 30, s, kRleWpb);
+}
+
+// Timed walks: launch_walk's chunking with the walk's own constants
+// (kDenseWaves / kDenseWpb, kRleWaves / kRleWpb); records as launch_walk_costs
+// reads them, the table as launch_walk_loads lays it out (tab == nullptr: no
+// loads).
+template <class Rows>
+static void launch_walk_timed(const uint2* adj, uint32_t shift, const Rows& rows,
+                              const uint32_t* wsets, uint32_t nsets, const uint32_t* qs,
+                              const uint32_t* qt, const uint32_t* qrow, const uint32_t* qperm,
+                              const uint64_t* depart, uint64_t period, const uint32_t* demand,
+                              uint32_t nq, uint32_t n, uint32_t limit, uint64_t* tab,
+                              uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                              unsigned long long* agg, uint32_t waves_target, uint32_t chunk_max,
+                              hipStream_t s, uint32_t wpb) {
+    const WalkShape sh = walk_shape(nq, waves_target, chunk_max, wpb);
+    const dim3 grid = sh.grid, blk = sh.blk;
+    const uint32_t c = sh.chunk;
+    const bool wide = weight_set_words(nsets) == 8u;
+    const uint32_t nslots = n << shift;  // also the zero record after the last slot
+    unsigned long long* t = reinterpret_cast<unsigned long long*>(tab);
+#define CPD_WALK_TIMED_F(SH, KW, LD)                                                            \
+    launch(kern::table_walk_timed<SH, KW, LD, Rows>, grid, blk, s, adj, rows, wsets, nslots, qs, \
+           qt, qrow, qperm, depart, demand, nq, c, limit, nsets, period, nslots, t, cost, hops, \
+           fin, agg)
+#define CPD_WALK_TIMED(SH)                              \
+    do {                                                \
+        if (wide && t) CPD_WALK_TIMED_F(SH, 8, true);   \
+        else if (wide) CPD_WALK_TIMED_F(SH, 8, false);  \
+        else if (t) CPD_WALK_TIMED_F(SH, 4, true);      \
+        else CPD_WALK_TIMED_F(SH, 4, false);            \
+    } while (0)
+    switch (shift) {
+        case 0: CPD_WALK_TIMED(0); break;
+        case 1: CPD_WALK_TIMED(1); break;
+        case 2: CPD_WALK_TIMED(2); break;
+        case 3: CPD_WALK_TIMED(3); break;
+        default: CPD_WALK_TIMED(4); break;
+    }
+#undef CPD_WALK_TIMED
+#undef CPD_WALK_TIMED_F
+}
+
+void launch_table_timed_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                              uint32_t npad, uint32_t lb, const uint32_t* wsets, uint32_t nsets,
+                              const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
+                              const uint32_t* qperm, const uint64_t* depart, uint64_t period,
+                              const uint32_t* demand, uint32_t nq, int32_t kmoves, uint32_t n,
+                              uint64_t* tab, uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                              unsigned long long* agg, hipStream_t s) {
+    const kern::DenseRows rows{dense, npad >> (5u - lb), kern::Tbl{lb}};
+    launch_walk_timed(reinterpret_cast<const uint2*>(adj), shift, rows, wsets, nsets, qs, qt, qrow,
+                      qperm, depart, period, demand, nq, n, walk_limit(kmoves, n), tab, cost, hops,
+                      fin, agg, kDenseWaves, 1024u, s, kDenseWpb);
+}
+
+void launch_table_timed(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                        const uint32_t* runs, const uint32_t* wsets, uint32_t nsets,
+                        const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
+                        const uint32_t* qperm, const uint64_t* depart, uint64_t period,
+                        const uint32_t* demand, uint32_t nq, int32_t kmoves, uint32_t n,
+                        uint64_t* tab, uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                        unsigned long long* agg, hipStream_t s) {
+    launch_walk_timed(reinterpret_cast<const uint2*>(adj), shift, kern::RleRows{offsets, runs},
+                      wsets, nsets, qs, qt, qrow, qperm, depart, period, demand, nq, n,
+                      walk_limit(kmoves, n), tab, cost, hops, fin, agg, kRleWaves, 1u << 30, s,
+                      kRleWpb);
 }
 
 void launch_loads_gather(const uint64_t* tab, const uint32_t* slot_of_edge, uint32_t m,

@@ -305,6 +305,29 @@ void launch_table_loads(const uint32_t* adj, uint32_t shift, const uint64_t* off
                         unsigned long long* agg, hipStream_t s);
 void launch_loads_gather(const uint64_t* tab, const uint32_t* slot_of_edge, uint32_t m,
                          uint32_t nslots, uint32_t nslices, uint64_t* out, hipStream_t s);
+// Timed walks (cpd_query_timed): the table-search walk once with a u64 clock
+// per query, started at depart[qperm[q]] (NULL: 0).  Move h is costed under
+// set j = min(clock / period, nsets - 1) of wsets (launch_table_costs'
+// records) and advances the clock by that weight; cost[q] = clock at the end -
+// departure.  tab != nullptr: demand[qperm[q]] (NULL: 1) is added to tab[j *
+// nslots + (column << shift) + move] as launch_table_loads adds it, nsets
+// planes; the caller zeroes tab or keeps what earlier launches left.  cost /
+// hops / fin in the sorted order of qs; agg as the walk's.  1 <= period <=
+// 2^60 and every departure < 2^63 (the caller checks).
+void launch_table_timed_dense(const uint32_t* adj, uint32_t shift, const uint32_t* dense,
+                              uint32_t npad, uint32_t lb, const uint32_t* wsets, uint32_t nsets,
+                              const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
+                              const uint32_t* qperm, const uint64_t* depart, uint64_t period,
+                              const uint32_t* demand, uint32_t nq, int32_t kmoves, uint32_t n,
+                              uint64_t* tab, uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                              unsigned long long* agg, hipStream_t s);
+void launch_table_timed(const uint32_t* adj, uint32_t shift, const uint64_t* offsets,
+                        const uint32_t* runs, const uint32_t* wsets, uint32_t nsets,
+                        const uint32_t* qs, const uint32_t* qt, const uint32_t* qrow,
+                        const uint32_t* qperm, const uint64_t* depart, uint64_t period,
+                        const uint32_t* demand, uint32_t nq, int32_t kmoves, uint32_t n,
+                        uint64_t* tab, uint64_t* cost, uint32_t* hops, uint8_t* fin,
+                        unsigned long long* agg, hipStream_t s);
 // out[perm[i] * k + j] = in[i * k + j] (k u64 per query, to the caller's order)
 void launch_scatter_u64_rows(const uint64_t* in, const uint32_t* perm, uint32_t nq, uint32_t k,
                              uint64_t* out, hipStream_t st);

@@ -11,6 +11,8 @@
 //                                           under the request's list of diffs)
 //             [--loads [--load-slices K --load-slice-moves S]]  (table-search
 //                                           only: also write every edge's load)
+//             [--timed P [--loads]]  (table-search only: cost, and load, every
+//                                     move under the diff of its clock time)
 //             [--verbose]  (per request on stderr: read+parse / prepare / compute)
 //
 // Creates its request FIFO, streams the CPD buckets this worker owns onto its
@@ -62,6 +64,19 @@
 // --load-slices K --load-slice-moves S the K time slices: move h of a walk
 // counts in slice min(h / S, K - 1) (written as .loads.tmp, renamed into
 // place).  The answer line and <query file>.res are what they are without it.
+// With --timed P (table-search only; 1 <= P <= 2^60, in weight units) every
+// request is answered through cpd_query_timed: the request's third field is
+// the diff list --costs reads ("-" = free flow, at most 8), diff j the state of
+// the network during [j P, (j + 1) P) of clock time, the last open-ended.
+// Query line q leaves at the q-th number of <query file>.dep — one unsigned
+// integer below 2^63 per query line, in the query file's order — or at 0 when
+// that file does not exist; a move is costed under the diff of the time its
+// edge is entered and advances the clock by that weight.  <query file>.res
+// gets "s t moves finished depart cost" per query in file order (written as
+// .res.tmp, renamed into place); "debug": true adds nothing.  With --loads as
+// well the call carries CPD_TIMED_LOADS (demand 1 per query line, not
+// accumulated across requests) and <query file>.loads holds the loaded edges
+// in the format above, one column per diff.  The answer line keeps its fields.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -229,6 +244,70 @@ static void write_loads(cpd_index* ix, const std::string& qfile, const cpd::io::
     }
 }
 
+// <query file>.dep of a --timed request: one unsigned integer per query line;
+// no such file: every query leaves at 0 (dep stays empty)
+static void read_departures(const std::string& qfile, size_t nq, std::vector<uint64_t>& dep) {
+    dep.clear();
+    const std::string path = qfile + ".dep";
+    std::FILE* f = std::fopen(path.c_str(), "r");
+    if (!f) {
+        if (errno == ENOENT) return;
+        throw std::runtime_error("cannot read " + path + ": " + std::strerror(errno));
+    }
+    std::string text;
+    char buf[65536];
+    for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, k);
+    std::fclose(f);
+    dep.reserve(nq);
+    size_t line = 1;
+    for (size_t p = 0; p < text.size(); ++line) {
+        size_t e = text.find('\n', p);
+        if (e == std::string::npos) e = text.size();
+        size_t a = p, b = e;
+        while (a < b && (text[a] == ' ' || text[a] == '\t')) ++a;
+        while (b > a && (text[b - 1] == ' ' || text[b - 1] == '\t' || text[b - 1] == '\r')) --b;
+        uint64_t v = 0;
+        bool ok = a < b;
+        for (size_t i = a; i < b && ok; ++i) {
+            const unsigned d = (unsigned)(text[i] - '0');
+            ok = d <= 9u && v <= (0xFFFFFFFFFFFFFFFFull - d) / 10u;
+            v = v * 10u + d;
+        }
+        if (!ok)
+            throw std::runtime_error(path + ": line " + std::to_string(line) +
+                                     " is not an unsigned integer");
+        dep.push_back(v);
+        p = e + 1;
+    }
+    if (dep.size() != nq)
+        throw std::runtime_error(path + ": " + std::to_string(dep.size()) + " departures for " +
+                                 std::to_string(nq) + " queries");
+}
+
+// <query file>.res of a --timed request: s t moves finished depart cost per query
+static void write_timed(cpd_index* ix, const std::string& qfile, const std::vector<uint32_t>& s,
+                        const std::vector<uint32_t>& t, const std::vector<uint64_t>& dep) {
+    const size_t nq = s.size();
+    std::vector<uint64_t> cost(nq);
+    std::vector<uint32_t> hops(nq);
+    std::vector<uint8_t> fin(nq);
+    if (cpd_query_timed_fetch(ix, cost.data(), hops.data(), fin.data()) != CPD_OK)
+        throw std::runtime_error(cpd_last_error());
+    const std::string path = qfile + ".res", tmp = path + ".tmp";
+    std::FILE* f = std::fopen(tmp.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    bool ok = true;
+    for (size_t q = 0; q < nq && ok; ++q)
+        ok = std::fprintf(f, "%u %u %u %u %llu %llu\n", s[q], t[q], hops[q], fin[q] == 1 ? 1u : 0u,
+                          (unsigned long long)(dep.empty() ? 0 : dep[q]),
+                          (unsigned long long)cost[q]) > 0;
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
+        ::unlink(tmp.c_str());
+        throw std::runtime_error("cannot write " + path);
+    }
+}
+
 static bool write_answer(const std::string& path, const std::string& line) {
     // process_query.send_remote mkfifo's the answer before writing the request
     // (process_query.py:72-73); tolerate a late mkfifo for up to 10 s
@@ -289,7 +368,17 @@ int main(int argc, char** argv) {
                      "                  cpd_query_loads (demand 1 per query) and write every "
                      "loaded edge to\n"
                      "                  <query file>.loads: edge from to load_0 ... load_{K-1}\n"
-                     "                  (K slices: move h counts in slice min(h / S, K - 1))\n");
+                     "                  (K slices: move h counts in slice min(h / S, K - 1))\n"
+                     "       [--timed P [--loads]]  table-search only: answer through "
+                     "cpd_query_timed; the\n"
+                     "                  request's diff field lists up to 8 diffs, diff j the "
+                     "network during clock\n"
+                     "                  time [j P, (j + 1) P); departures from <query file>.dep "
+                     "(one per query\n"
+                     "                  line; absent: 0); <query file>.res gets, per query:\n"
+                     "                  s t moves finished depart cost\n"
+                     "                  (with --loads <query file>.loads has one column per "
+                     "diff)\n");
         return 2;
     }
     // table-search (make_fifos.py:20) or the CPD-heuristic search
@@ -329,6 +418,19 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "fifo_auto: --loads needs --alg table-search without --paths or "
                              "--costs (a cpd-search's route is not the walk's; --paths and --costs "
                              "answer through cpd_query_paths and cpd_query_costs)\n");
+        return 2;
+    }
+    const bool timed = a.has("timed");
+    if (timed && (search || paths || costs || a.has("load-slices") || a.has("load-slice-moves"))) {
+        std::fprintf(stderr, "fifo_auto: --timed needs --alg table-search without --paths, --costs, "
+                             "--load-slices or --load-slice-moves (a cpd-search's route is not the "
+                             "walk's; --paths and --costs answer through cpd_query_paths and "
+                             "cpd_query_costs; a timed walk's load planes are its diffs)\n");
+        return 2;
+    }
+    const long long period = a.num("timed", 0);
+    if (timed && (period < 1 || period > (1ll << 60))) {
+        std::fprintf(stderr, "fifo_auto: --timed P needs 1 <= P <= 2^60\n");
         return 2;
     }
     const long long load_slices = a.num("load-slices", 1), load_slice_moves = a.num("load-slice-moves", 0);
@@ -600,8 +702,10 @@ int main(int argc, char** argv) {
             // kept across requests: their pages stay mapped
             static std::vector<uint32_t> s, t;
             cpd::io::read_query_file(qfile, parse_threads, s, t);
+            static std::vector<uint64_t> dep;
+            if (timed) read_departures(qfile, s.size(), dep);
             const double t_read = now() - t0;
-            if (costs) {
+            if (costs || timed) {
                 // the diff field is a list: its sets, loaded beside (and
                 // independent of) the index's current weights
                 if (diff != active_sets) {
@@ -664,6 +768,12 @@ int main(int argc, char** argv) {
                 rc = cpd_query_costs(ix, k_moves, (uint32_t)slice_moves, &st);
                 if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
                 write_costs(ix, qfile, s, t, slice_moves ? 1u : active_nsets);
+            } else if (timed) {
+                rc = cpd_query_timed(ix, k_moves, dep.empty() ? nullptr : dep.data(),
+                                     (uint64_t)period, nullptr, loads ? CPD_TIMED_LOADS : 0u, &st);
+                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                write_timed(ix, qfile, s, t, dep);
+                if (loads) write_loads(ix, qfile, g, active_nsets);
             } else if (loads) {
                 rc = cpd_query_loads(ix, k_moves, nullptr, (uint32_t)load_slices,
                                      (uint32_t)load_slice_moves, 0, &st);
@@ -679,7 +789,7 @@ int main(int argc, char** argv) {
                 rc = cpd_query_run(ix, k_moves, &st);
                 if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
             }
-            if (debug && !costs) {
+            if (debug && !costs && !timed) {
                 std::vector<uint64_t> cost(nq);
                 std::vector<uint32_t> hops(nq);
                 std::vector<uint8_t> fin(nq);

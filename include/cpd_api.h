@@ -483,7 +483,8 @@ int  cpd_query_costs_fetch(cpd_index* ix, uint64_t* costs, uint32_t* hops, uint8
  * to what earlier calls on this index left (nothing: it starts from zero),
  * across cpd_query_prepare calls — a demand set larger than a batch goes
  * through in pieces, and workers' tables add up on the head; CPD_E_ARG when
- * nslices or slice_moves differ from the resident table's.
+ * nslices or slice_moves differ from the resident table's, or that table is
+ * a timed walk's (cpd_query_timed).
  * Also does what cpd_query_run does (st, and cpd_query_fetch afterwards
  * returns this walk's cost / hops / finished under the index's current
  * weights) and, like it, ends the validity of fetched paths.
@@ -509,6 +510,63 @@ int  cpd_query_loads(cpd_index* ix, int32_t k_moves, const uint32_t* demand /* n
                      uint32_t flags, cpd_query_stats* st);
 int  cpd_query_loads_fetch(cpd_index* ix, uint64_t* loads /* nslices * m */);
 int  cpd_query_loads_clear(cpd_index* ix);
+
+/* Timed walks — the time axis of the two above.  cpd_query_costs' sliced mode
+ * and cpd_query_loads pick the congestion state of a move by its move NUMBER;
+ * a weight set is the state of the network during an interval of TIME (the
+ * reference is a "Time-Dependant-Oracle-Search", process_query.py:250).  Here
+ * every query carries a clock that starts at its departure and advances with
+ * the cost being summed, and a move is costed — and loaded — under the set of
+ * the interval in which its edge is entered.
+ * cpd_query_timed: on the queries of the last cpd_query_prepare, the walk of
+ * cpd_query_run (k_moves with its meaning, the n-move loop guard, the rule
+ * that a move naming no out-edge stops the walk, and the k_moves = 0 refill
+ * limit described at cpd_query_paths); the route never depends on the
+ * weights.  With the K sets W_0 .. W_{K-1} of cpd_index_set_weight_sets, a
+ * period P (in weight units) and tau_0 = depart[q] (nq values, u64, weight
+ * units, the CALLER's query order; NULL = 0 for every query), move number h
+ * on original edge e_h does
+ *     j_h       = min(tau_h / P, K - 1)   (integer division: tau_h == k P
+ *                                          belongs to set k)
+ *     c_h       = W_{j_h}[e_h]
+ *     tau_{h+1} = tau_h + c_h
+ * — the weight is frozen when the edge is entered (piecewise constant; one
+ * heavy edge may cross several periods).  Per query cost = tau_end - depart[q]
+ * (u64), hops and finished as the plain walk's.  K = 1, or P beyond every
+ * arrival, is cpd_query_costs' column 0.
+ * flags & CPD_TIMED_LOADS: demand[q] (nq values, caller order; NULL = 1 each;
+ * not read without the flag) is added to counter (j_h, e_h) of the index's
+ * load table for every move taken: K planes of m 64-bit counters, e the
+ * original edge index as in cpd_query_loads, fetched by cpd_query_loads_fetch
+ * (K * m values) and dropped by cpd_query_loads_clear.  The table remembers
+ * its kind: without CPD_LOADS_ACCUMULATE it is made again and zeroed; with it
+ * the resident table must be a timed one of the same K and period (none
+ * resident: the call starts from zero), else CPD_E_ARG and the table stays —
+ * and cpd_query_loads(.., CPD_LOADS_ACCUMULATE) onto a timed table is
+ * CPD_E_ARG too.  Load the demand per interval here, turn the loads into
+ * weight sets, cost the demand again: a traffic-assignment loop.
+ * P must be in [1, 2^60] and every departure below 2^63 (a walk adds less
+ * than n < 2^28 moves x 2^32, so the clock and (j + 1) P never wrap):
+ * CPD_E_ARG otherwise, the message naming the first offending value.
+ * CPD_E_ARG also when no sets are loaded, the index is incomplete, or
+ * CPD_LOADS_ACCUMULATE comes without CPD_TIMED_LOADS.
+ * st: queries / finished / hops as cpd_query_run reports them, cost = the sum
+ * of the costs, kernel_ms of this walk.  The results live in buffers of their
+ * own: what cpd_query_fetch, cpd_query_paths_fetch and cpd_query_costs_fetch
+ * return is left as it was, and fetched paths stay valid.
+ * cpd_query_timed_fetch: cost / hops / finished in the CALLER's query order;
+ * any pointer may be NULL; scattered to the caller's order on the GPU as
+ * cpd_query_costs_fetch does.  CPD_E_ARG before a cpd_query_timed on the
+ * prepared queries.  Both answer the empty batch.
+ * Arena: the result buffers and the table are carved as cpd_query_costs' and
+ * cpd_query_loads' are.                                                     */
+#define CPD_TIMED_LOADS 2u        /* a bit of its own beside CPD_LOADS_ACCUMULATE */
+int  cpd_query_timed(cpd_index* ix, int32_t k_moves,
+                     const uint64_t* depart /* nq, caller order; NULL = 0 */, uint64_t period,
+                     const uint32_t* demand /* nq; NULL = 1; read only with CPD_TIMED_LOADS */,
+                     uint32_t flags /* CPD_TIMED_LOADS | CPD_LOADS_ACCUMULATE */,
+                     cpd_query_stats* st);
+int  cpd_query_timed_fetch(cpd_index* ix, uint64_t* cost, uint32_t* hops, uint8_t* finished);
 void cpd_index_free(cpd_index* ix);
 
 /* [gpu] CPD-heuristic search — fifo_auto's other algorithm family
