@@ -60,7 +60,7 @@ EXPORTED = [
     "cpd_rows_move_bits", "cpd_graph_move_bits", "cpd_bucket_bytes", "cpd_space_check",
     "cpd_query_paths", "cpd_query_paths_fetch", "cpd_query_search_paths",
     "cpd_index_set_weight_sets", "cpd_query_costs", "cpd_query_costs_fetch",
-    "cpd_query_loads", "cpd_query_loads_fetch", "cpd_query_loads_clear",
+    "cpd_query_loads", "cpd_query_loads_fetch", "cpd_query_loads_clear", "cpd_query_search_loads",
     "cpd_query_timed", "cpd_query_timed_fetch",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
@@ -113,6 +113,12 @@ class SearchStats(C.Structure):
 class SearchPathsInfo(C.Structure):
     _fields_ = [("nodes", C.c_uint64), ("prefix_nodes", C.c_uint64),
                 ("prefix_bytes", C.c_uint64), ("paths_ms", C.c_double)]
+
+
+class SearchLoadsInfo(C.Structure):
+    _fields_ = [("moves", C.c_uint64), ("prefix_moves", C.c_uint64),
+                ("prefix_nodes", C.c_uint64), ("prefix_bytes", C.c_uint64),
+                ("loads_ms", C.c_double)]
 
 
 class KernelTime(C.Structure):
@@ -901,6 +907,56 @@ class Index:
         d = {k: getattr(st, k) for k, _ in SearchStats._fields_}
         d["paths"] = {k: getattr(info, k) for k, _ in SearchPathsInfo._fields_}
         return offsets, d
+
+    def search_loads(self, s, t, demand=None, accumulate: bool = False, prefix_bytes=0,
+                     hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0, capacity=0,
+                     virtual_tick_ns=0, tables="auto", workspace_frac=0.0, capacity_max=0):
+        """search() with the demand every edge carries when the routes found
+        are loaded (cpd_query_search_loads): (loads u64[1, m], cost, plen,
+        finished, counters[nq, 5], stats).  demand: one u32 per query (None =
+        1 each), added to loads[0, e] for every edge e (original index) of the
+        route search_paths() returns for a query with finished == 1 — on the
+        A* tree's chain the cheapest edge under the current weights between
+        the two nodes (the first of equals), on the CPD walk the edge the
+        row's move names.  accumulate=True adds to a resident one-plane table
+        (loads(), earlier search_loads()).  stats holds the search's and,
+        under "loads", moves / prefix_moves / prefix_nodes / prefix_bytes /
+        loads_ms.  prefix_bytes as for search_paths(): too small raises
+        CpdError(CPD_E_OOM) naming the bytes needed, the table untouched and
+        the search's results still fetchable (search_fetch)."""
+        self.prepare(s, t)
+        st = self.search_loads_run(demand, accumulate, prefix_bytes, hscale, fscale, k_moves,
+                                   itrs, time_ns, capacity, virtual_tick_ns, tables,
+                                   workspace_frac, capacity_max)
+        cost, plen, fin, cnt = self.search_fetch()
+        return self.loads_fetch(), cost, plen, fin, cnt, st
+
+    def search_loads_run(self, demand=None, accumulate: bool = False, prefix_bytes=0, hscale=1.0,
+                         fscale=0.0, k_moves=-1, itrs=-1, time_ns=0, capacity=0,
+                         virtual_tick_ns=0, tables="auto", workspace_frac=0.0, capacity_max=0,
+                         flags=None):
+        """cpd_query_search_loads on the prepared queries: stats (flags: the
+        call's flag word, instead of the one accumulate gives)."""
+        self._path_offsets = None
+        d = None
+        if demand is not None:
+            d = _u32(demand)
+            if d.shape != (self._nq,):
+                raise ValueError("demand must have one entry per prepared query")
+        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
+                       int(capacity), int(virtual_tick_ns), SEARCH_FORMS[tables],
+                       float(workspace_frac), int(capacity_max))
+        st = SearchStats()
+        info = SearchLoadsInfo()
+        if flags is None:
+            flags = LOADS_ACCUMULATE if accumulate else 0
+        _check(lib.cpd_query_search_loads(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)),
+                                          _ptr(d, u32p), C.c_uint32(flags), C.byref(st),
+                                          C.byref(info)))
+        self._load_slices = 1
+        out = {k: getattr(st, k) for k, _ in SearchStats._fields_}
+        out["loads"] = {k: getattr(info, k) for k, _ in SearchLoadsInfo._fields_}
+        return out
 
     def search_fetch(self):
         """(cost, plen, finished, counters[nq, 5]) of the last search on the

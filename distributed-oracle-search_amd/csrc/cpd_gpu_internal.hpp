@@ -510,7 +510,8 @@ struct cpd_index {
     // ld_period: non-zero for a table cpd_query_timed filled — its planes are
     // the intervals [j * ld_period, (j + 1) * ld_period) of clock time, the
     // last open-ended, ld_slices = the sets it was filled under, ld_slice_moves
-    // = 0; a table is of one kind, accumulated into only by its own.
+    // = 0; a table is of one kind, accumulated into only by its own
+    // (cpd_query_search_loads fills and adds to the one-plane kind).
     // The batch's demand (caller order) and the fetch's edge-order copy.  The
     // table is carved from the arena when one is committed (see wsets above).
     DevBuf<uint64_t> ld_tab, ld_out;
@@ -525,7 +526,7 @@ struct cpd_index {
     DevBuf<uint32_t> tm_hops;
     DevBuf<uint8_t> tm_fin;
     bool timed_ready = false;
-    // search paths (cpd_query_search_paths), scratch of one call, freed when
+    // search paths (cpd_query_search_paths, _search_loads), scratch of one call, freed when
     // it returns (the cursor stays): the prefix pool and its cursor;
     // per query (sorted order) the prefix's place and length, v* and lw(v*);
     // the suffix walk's offset pairs and their index (search_path_plan)
@@ -580,4 +581,6 @@ namespace cpd {
 // Helpers that cross the units (defined in the unit named).
 void fold_late(cpd_graph* g, size_t keep);  // cpd_rows.cpp
 void ensure_dense(cpd_index* ix);           // cpd_index.cpp
+void reset_load_table(cpd_index* ix, uint32_t planes, uint32_t slice_moves,
+                      uint64_t period);     // cpd_index.cpp
 }  // namespace cpd

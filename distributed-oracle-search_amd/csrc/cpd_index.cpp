@@ -576,6 +576,25 @@ void ensure_slot_of_edge(cpd_graph* g) {
 
 }  // namespace
 
+// The resident load table made again: `planes` zeroed planes of the kind given
+// (slice_moves and period as cpd_index keeps them), from the arena when one is
+// committed.
+void cpd::reset_load_table(cpd_index* ix, uint32_t planes, uint32_t slice_moves, uint64_t period) {
+    cpd_graph* g = ix->g;
+    const uint32_t nslots = g->n << g->adj_shift;
+    ensure_slot_of_edge(g);
+    ix->loads_ready = false;
+    {
+        ArenaScope carve;
+        ix->ld_tab.alloc((size_t)planes * nslots);
+    }
+    HIP_CHECK(hipMemsetAsync(ix->ld_tab.p, 0, (size_t)planes * nslots * sizeof(uint64_t), g->stream));
+    ix->ld_slices = planes;
+    ix->ld_slice_moves = slice_moves;
+    ix->ld_period = period;
+    ix->loads_ready = true;
+}
+
 // Expand the resident RLE rows into dense move tables (once per index).
 void cpd::ensure_dense(cpd_index* ix) {
     cpd_graph* g = ix->g;
@@ -899,23 +918,10 @@ int cpd_query_loads(cpd_index* ix, int32_t k_moves, const uint32_t* demand, uint
         const size_t stride = (size_t)1 << g->adj_shift;
         // the kernel keeps a slot as u32, 0xFFFFFFFF = none
         CPD_REQUIRE(stride * g->n < 0xFFFFFFFFull, CPD_E_RANGE, "loads: 2^32 adjacency slots or more");
-        const uint32_t nslots = g->n << g->adj_shift;
         ix->paths_ready = false;
         const bool dense = ix->use_dense();
         if (dense && !ix->dense_ready) ensure_dense(ix);
-        ensure_slot_of_edge(g);
-        if (!keep) {
-            ix->loads_ready = false;
-            {
-                ArenaScope carve;
-                ix->ld_tab.alloc((size_t)nslices * nslots);
-            }
-            HIP_CHECK(hipMemsetAsync(ix->ld_tab.p, 0, (size_t)nslices * nslots * sizeof(uint64_t), s));
-            ix->ld_slices = nslices;
-            ix->ld_slice_moves = slice_moves;
-            ix->ld_period = 0;
-            ix->loads_ready = true;
-        }
+        if (!keep) reset_load_table(ix, nslices, slice_moves, 0);
         if (demand && nq) ix->ld_demand.upload(demand, nq, s);
         const uint32_t* dem = demand && nq ? ix->ld_demand.p : nullptr;
         HIP_CHECK(hipMemsetAsync(ix->agg.p, 0, 3 * sizeof(unsigned long long), s));
@@ -1030,7 +1036,6 @@ int cpd_query_timed(cpd_index* ix, int32_t k_moves, const uint64_t* depart, uint
         // the kernel keeps a slot as u32, 0xFFFFFFFF = none
         CPD_REQUIRE(!loads || stride * g->n < 0xFFFFFFFFull, CPD_E_RANGE,
                     "timed: 2^32 adjacency slots or more");
-        const uint32_t nslots = g->n << g->adj_shift;
         ix->timed_ready = false;
         const bool dense = ix->use_dense();
         if (dense && !ix->dense_ready) ensure_dense(ix);
@@ -1041,21 +1046,7 @@ int cpd_query_timed(cpd_index* ix, int32_t k_moves, const uint64_t* depart, uint
             ix->tm_hops.alloc(m);
             ix->tm_fin.alloc(m);
         }
-        if (loads) {
-            ensure_slot_of_edge(g);
-            if (!keep) {
-                ix->loads_ready = false;
-                {
-                    ArenaScope carve;
-                    ix->ld_tab.alloc((size_t)nsets * nslots);
-                }
-                HIP_CHECK(hipMemsetAsync(ix->ld_tab.p, 0, (size_t)nsets * nslots * sizeof(uint64_t), s));
-                ix->ld_slices = nsets;
-                ix->ld_slice_moves = 0;
-                ix->ld_period = period;
-                ix->loads_ready = true;
-            }
-        }
+        if (loads && !keep) reset_load_table(ix, nsets, 0, period);
         if (depart && nq) ix->tm_depart.upload(depart, nq, s);
         const uint64_t* dep = depart && nq ? ix->tm_depart.p : nullptr;
         if (loads && demand && nq) ix->ld_demand.upload(demand, nq, s);

@@ -4995,6 +4995,78 @@ __global__ __launch_bounds__(256) void search_path_join(const uint32_t* __restri
     }
 }
 
+// Search loads (cpd_query_search_loads): the edge of every prefix move, loaded.
+// Pair k of sorted query i is a = pool[poff + k] -> b = pool[poff + k + 1], b's
+// parent being a.  The edge that set g(b) is, among a's out-edges with head b,
+// the one of least selected weight, the first of them on ties: a relaxation
+// scans the out-list in order and replaces g only by a strictly smaller value.
+// So the row a of adj_w — the adjacency the search ran on — is scanned in slot
+// order for the first slot with dst == b of least weight, and the query's
+// demand goes to counter (a << SHIFT) + slot of plane 0 with loads_add: one
+// atomic per move, as the walks'.  A wave per query, a lane per pair, striding
+// as search_path_join does; the demand is read once per wave; the row comes in
+// with the widest loads its size allows (8 B for one slot, 16 B for two, uint4
+// pairs above); no LDS, no lane depends on another.  cnt[0] += the adds made,
+// cnt[1] += the pairs without an edge (none if the search is right: the host
+// fails the call on them, nothing is guessed) — a wave's sums, one atomic each.
+template <int SHIFT>
+__global__ __launch_bounds__(256) void search_prefix_loads(
+    const uint2* __restrict__ adj_w, const uint32_t* __restrict__ pool,
+    const unsigned long long* __restrict__ poff, const uint32_t* __restrict__ pn,
+    const uint32_t* __restrict__ qperm, const uint32_t* __restrict__ demand, uint32_t nq,
+    uint32_t nslots, unsigned long long* __restrict__ tab, unsigned long long* __restrict__ cnt) {
+    constexpr int NP = SHIFT >= 1 ? (1 << SHIFT) / 2 : 1;  // 16-B pieces of a row
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    unsigned long long adds = 0, lost = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < nq;
+         i += waves) {
+        const uint32_t p = pn[i];
+        if (p < 2u) continue;
+        const uint32_t dem = demand ? demand[qperm[i]] : 1u;
+        const uint32_t* __restrict__ src = pool + poff[i];
+        for (uint32_t k = lane; k < p - 1u; k += 64u) {
+            const uint32_t a = src[k], b = src[k + 1u];
+            uint32_t best = kNoSlot, bw = 0;
+            auto take = [&](uint32_t slot, uint32_t d, uint32_t w) {
+                if (d == b && (best == kNoSlot || w < bw)) {
+                    best = slot;
+                    bw = w;
+                }
+            };
+            if constexpr (SHIFT == 0) {
+                const uint2 e = adj_w[a];
+                take(0u, e.x, e.y);
+            } else {
+                const uint4* a4 = reinterpret_cast<const uint4*>(adj_w) + (size_t)a * NP;
+                uint4 r[NP];
+#pragma unroll
+                for (int j = 0; j < NP; ++j) r[j] = a4[j];
+#pragma unroll
+                for (int j = 0; j < NP; ++j) {
+                    take(2u * j, r[j].x, r[j].y);
+                    take(2u * j + 1u, r[j].z, r[j].w);
+                }
+            }
+            if (best != kNoSlot) {
+                loads_add(tab, nslots, (a << SHIFT) + best, 0u, dem);
+                ++adds;
+            } else {
+                ++lost;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        adds += __shfl_xor(adds, o, 64);
+        lost += __shfl_xor(lost, o, 64);
+    }
+    if (lane == 0) {
+        if (adds) atomicAdd(&cnt[0], adds);
+        if (lost) atomicAdd(&cnt[1], lost);
+    }
+}
+
 }  // namespace kern
 
 // ---------------------------------------------------------------------------
@@ -5824,6 +5896,30 @@ void launch_search_path_join(const uint32_t* pool, const unsigned long long* pof
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)nq + 3u) / 4u, 16384u);
     launch(kern::search_path_join, dim3(blocks), dim3(256), st, pool, poff, pn, qperm, off,
            node_of_col, nq, nodes);
+}
+
+void launch_search_prefix_loads(const uint32_t* adj_w, uint32_t shift, const uint32_t* pool,
+                                const unsigned long long* poff, const uint32_t* pn,
+                                const uint32_t* qperm, const uint32_t* demand, uint32_t nq,
+                                uint32_t n, uint64_t* tab, unsigned long long* cnt,
+                                hipStream_t st) {
+    if (!nq) return;
+    // search_path_join's shape: four waves a workgroup, a query a wave, striding
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)nq + 3u) / 4u, 16384u);
+    const uint2* adj = reinterpret_cast<const uint2*>(adj_w);
+    unsigned long long* t = reinterpret_cast<unsigned long long*>(tab);
+    const uint32_t nslots = n << shift;
+#define CPD_PREFIX_LOADS(SH)                                                                  \
+    launch(kern::search_prefix_loads<SH>, dim3(blocks), dim3(256), st, adj, pool, poff, pn, \
+           qperm, demand, nq, nslots, t, cnt)
+    switch (shift) {
+        case 0: CPD_PREFIX_LOADS(0); break;
+        case 1: CPD_PREFIX_LOADS(1); break;
+        case 2: CPD_PREFIX_LOADS(2); break;
+        case 3: CPD_PREFIX_LOADS(3); break;
+        default: CPD_PREFIX_LOADS(4); break;
+    }
+#undef CPD_PREFIX_LOADS
 }
 
 }  // namespace cpd

@@ -409,5 +409,19 @@ void launch_search_path_join(const uint32_t* pool, const unsigned long long* pof
                              const uint32_t* pn, const uint32_t* qperm, const uint64_t* off,
                              const uint32_t* node_of_col, uint32_t nq, uint32_t* nodes,
                              hipStream_t st);
+// Search loads (cpd_query_search_loads), the prefix moves: for every pair of
+// consecutive columns a -> b of sorted query i's prefix (pool / poff / pn as
+// the PATHS launch left them; every prefix stored: *top <= cap), demand[
+// qperm[i]] (NULL: 1) is added to tab[(a << shift) + slot], slot = the first
+// slot of adj_w's row a with head b of least weight — plane 0 of a table laid
+// out as launch_table_loads lays it, n << shift counters.  cnt[0] += the adds
+// made, cnt[1] += the pairs without such an edge (an internal error: nothing
+// is added for them); the caller zeroes both.  The suffix moves are
+// launch_table_loads_dense from vcol.
+void launch_search_prefix_loads(const uint32_t* adj_w, uint32_t shift, const uint32_t* pool,
+                                const unsigned long long* poff, const uint32_t* pn,
+                                const uint32_t* qperm, const uint32_t* demand, uint32_t nq,
+                                uint32_t n, uint64_t* tab, unsigned long long* cnt,
+                                hipStream_t st);
 
 }  // namespace cpd

@@ -507,6 +507,21 @@ uint64_t run_search(cpd_index* ix, const cpd_search_opts* opts, cpd_search_stats
     return used;
 }
 
+// The prefix pool and the per-query records are scratch of one PATHS call
+// (cpd_query_search_paths, cpd_query_search_loads): freed however it ends (as
+// the spill pools are), so that a later search on the index is sized from the
+// same HBM as before.
+struct PathsScratch {
+    cpd_index* ix;
+    ~PathsScratch() {
+        for (DevBuf<uint32_t>* b : {&ix->spp_pool, &ix->spp_pn, &ix->spp_vcol, &ix->spp_vlw,
+                                    &ix->spp_wperm})
+            b->release();
+        ix->spp_off.release();
+        ix->spp_woff.release();
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -526,19 +541,7 @@ int cpd_query_search_paths(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
         CPD_REQUIRE(nq < 0x7FFFFFFFu, CPD_E_RANGE, "search paths: too many queries for one batch");
         ix->paths_ready = false;
         if (info) *info = cpd_search_paths_info{0, 0, 0, 0.0};
-        // the prefix pool and the per-query records are scratch of this call:
-        // freed however it ends (as the spill pools are), so that a later
-        // search on the index is sized from the same HBM as before
-        struct Scratch {
-            cpd_index* ix;
-            ~Scratch() {
-                for (DevBuf<uint32_t>* b : {&ix->spp_pool, &ix->spp_pn, &ix->spp_vcol,
-                                            &ix->spp_vlw, &ix->spp_wperm})
-                    b->release();
-                ix->spp_off.release();
-                ix->spp_woff.release();
-            }
-        } scratch{ix};
+        PathsScratch scratch{ix};
         uint64_t pool_bytes = prefix_bytes;
         const uint64_t used = run_search(ix, opts, st, true, &pool_bytes);
         if (info) {
@@ -623,6 +626,99 @@ int cpd_query_search_paths(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
         }
         std::memcpy(offsets, ix->poff_h.data(), ((size_t)nq + 1u) * sizeof(uint64_t));
         ix->paths_ready = true;
+    });
+}
+
+int cpd_query_search_loads(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                           const uint32_t* demand, uint32_t flags, cpd_search_stats* st,
+                           cpd_search_loads_info* info) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "search loads: null index");
+        CPD_REQUIRE(!(flags & ~CPD_LOADS_ACCUMULATE), CPD_E_ARG,
+                    "search loads: unknown flag bits " + std::to_string(flags & ~CPD_LOADS_ACCUMULATE));
+        if (info) *info = cpd_search_loads_info{0, 0, 0, 0, 0.0};
+        const bool keep = (flags & CPD_LOADS_ACCUMULATE) && ix->loads_ready;
+        CPD_REQUIRE(!keep || !ix->ld_period, CPD_E_ARG,
+                    "search loads: accumulate into the table of a timed walk (period " +
+                        std::to_string(ix->ld_period) + ")");
+        CPD_REQUIRE(!keep || (ix->ld_slices == 1 && ix->ld_slice_moves == 0), CPD_E_ARG,
+                    "search loads: accumulate into a table of " + std::to_string(ix->ld_slices) +
+                        " slices of " + std::to_string(ix->ld_slice_moves) +
+                        " moves: a search loads one plane");
+        cpd_graph* g = ix->g;
+        // the kernels keep a slot as u32, 0xFFFFFFFF = none
+        CPD_REQUIRE(((uint64_t)g->n << g->adj_shift) < 0xFFFFFFFFull, CPD_E_RANGE,
+                    "search loads: 2^32 adjacency slots or more");
+        const uint32_t nq = ix->nq;
+        ix->paths_ready = false;
+        PathsScratch scratch{ix};
+        uint64_t pool_bytes = prefix_bytes;
+        const uint64_t used = run_search(ix, opts, st, true, &pool_bytes);
+        if (info && nq) {
+            info->prefix_nodes = used;
+            info->prefix_bytes = pool_bytes;
+        }
+        // the search's results are whole and fetchable from here on; the load
+        // table is touched only once every prefix is known to be stored
+        CPD_REQUIRE(used <= pool_bytes / 4u, CPD_E_OOM,
+                    "search loads: the prefixes need " + std::to_string(4ull * used) +
+                        " bytes of prefix pool, " + std::to_string(pool_bytes) +
+                        " were given: call again with prefix_bytes >= " +
+                        std::to_string(4ull * used));
+        if (!keep) reset_load_table(ix, 1, 0, 0);
+        if (!nq) return;
+        hipStream_t s = g->stream;
+        if (demand) ix->ld_demand.upload(demand, nq, s);
+        const uint32_t* dem = demand ? ix->ld_demand.p : nullptr;
+        // the suffix walk's cost / hops / fin go nowhere: the index's hold the
+        // search's.  cnt: the walk's sums (finished, moves, cost: wave_stats),
+        // then the prefix kernel's adds and its pairs without an edge
+        DevBuf<uint64_t> w_cost;
+        DevBuf<uint32_t> w_hops;
+        DevBuf<uint8_t> w_fin;
+        DevBuf<unsigned long long> cnt;
+        w_cost.alloc(nq);
+        w_hops.alloc(nq);
+        w_fin.alloc(nq);
+        cnt.alloc(5);
+        HIP_CHECK(hipMemsetAsync(cnt.p, 0, 5 * sizeof(unsigned long long), s));
+        const uint32_t* adj_w = ix->custom_w ? ix->adj_sel.p : g->adj.p;
+        Events<2> ev(g);
+        HIP_CHECK(hipEventRecord(ev.e[0], s));
+        (void)hipGetLastError();
+        launch_search_prefix_loads(adj_w, g->adj_shift, ix->spp_pool.p, ix->spp_off.p,
+                                   ix->spp_pn.p, ix->qperm.p, dem, nq, g->n, ix->ld_tab.p,
+                                   cnt.p + 3, s);
+        // a query without a route has vcol = t: no move
+        launch_table_loads_dense(adj_w, g->adj_shift, ix->dense.p, g->npad, g->tlb, ix->spp_vcol.p,
+                                 ix->qt.p, ix->qrow.p, ix->qperm.p, dem, nq, -1, g->n, 1u, 0u,
+                                 ix->ld_tab.p, w_cost.p, w_hops.p, w_fin.p, cnt.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ev.e[1], s));
+        unsigned long long h[5] = {0, 0, 0, 0, 0};
+        HIP_CHECK(hipMemcpyAsync(h, cnt.p, sizeof h, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (h[4]) {
+            ix->loads_ready = false;  // some moves are missing from it
+            throw Error(CPD_E_HIP, "search loads: internal error: " + std::to_string(h[4]) +
+                                       " prefix moves name no edge of the adjacency searched");
+        }
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        if (g->timing) {
+            // per move one 8-B counter; the prefixes read, a row per prefix
+            // move; the suffix walk's own bytes are not modelled
+            Agg& ag = g->agg["search_loads"];
+            ag.launches += 2;
+            ag.ms += ms;
+            ag.bytes += 8.0 * (double)(h[1] + h[3]) + 4.0 * (double)used +
+                        8.0 * (double)((uint64_t)h[3] << g->adj_shift);
+        }
+        if (info) {
+            info->moves = h[1] + h[3];
+            info->prefix_moves = h[3];
+            info->loads_ms = ms;
+        }
     });
 }
 

@@ -7,6 +7,7 @@
 //             [--index auto|rle|dense] [--read-threads T] [--parse-threads P]
 //             [--paths]  (table-search only: also write every walk's nodes)
 //             [--search-paths]  (cpd-search only: also write every route's nodes)
+//             [--search-loads]  (cpd-search only: also write every edge's load)
 //             [--costs [--slice-moves S]]  (table-search only: cost every walk
 //                                           under the request's list of diffs)
 //             [--loads [--load-slices K --load-slice-moves S]]  (table-search
@@ -46,6 +47,12 @@
 // cpd_query_search_paths and <query file>.paths holds the search paths in
 // the same format: the A* tree's chain from s to the incumbent's node, then
 // the CPD walk to t; "s t 0 0" (no nodes) for a query without a route.
+// With --search-loads (cpd-search only, not with --search-paths) every request
+// is answered through cpd_query_search_loads with a demand of 1 per query
+// line, not accumulated across requests, and <query file>.loads holds the
+// loaded edges of the routes found under the request's diff, in the format
+// of --loads below with one column.  The answer line and <query file>.res are
+// what they are without it.
 // With --costs (table-search only) the request's third field may be a
 // comma-separated list of up to 8 diff files, "-" = free flow (e.g.
 // "-,a.diff,b.diff"); the walk runs once (cpd_query_costs) and <query
@@ -353,6 +360,11 @@ int main(int argc, char** argv) {
                      "cpd_query_search_paths and\n"
                      "                  write every route's nodes to <query file>.paths, same "
                      "format\n"
+                     "       [--search-loads]  cpd-search only: answer through "
+                     "cpd_query_search_loads (demand 1\n"
+                     "                  per query) and write every loaded edge of the routes "
+                     "found to\n"
+                     "                  <query file>.loads: edge from to load\n"
                      "       [--costs [--slice-moves S]]  table-search only: the request's diff "
                      "field may list\n"
                      "                  up to 8 diffs (\"-,a.diff,b.diff\"); one walk costs every "
@@ -416,7 +428,8 @@ int main(int argc, char** argv) {
     const bool loads = a.has("loads");
     if (loads && (search || paths || costs)) {
         std::fprintf(stderr, "fifo_auto: --loads needs --alg table-search without --paths or "
-                             "--costs (a cpd-search's route is not the walk's; --paths and --costs "
+                             "--costs (a cpd-search's route is not the walk's: --search-loads loads "
+                             "it; --paths and --costs "
                              "answer through cpd_query_paths and cpd_query_costs)\n");
         return 2;
     }
@@ -431,6 +444,14 @@ int main(int argc, char** argv) {
     const long long period = a.num("timed", 0);
     if (timed && (period < 1 || period > (1ll << 60))) {
         std::fprintf(stderr, "fifo_auto: --timed P needs 1 <= P <= 2^60\n");
+        return 2;
+    }
+    const bool search_loads = a.has("search-loads");
+    if (search_loads && (!search || search_paths || a.has("load-slices") || a.has("load-slice-moves"))) {
+        std::fprintf(stderr, "fifo_auto: --search-loads needs --alg cpd-search without --search-paths, "
+                             "--load-slices or --load-slice-moves (the walks of a table-search are "
+                             "loaded with --loads; --search-paths answers through "
+                             "cpd_query_search_paths; a search loads one plane)\n");
         return 2;
     }
     const long long load_slices = a.num("load-slices", 1), load_slice_moves = a.num("load-slice-moves", 0);
@@ -756,11 +777,14 @@ int main(int argc, char** argv) {
                 if (search_paths) {
                     spoff.resize(nq + 1);
                     rc = cpd_query_search_paths(ix, &so, 0, spoff.data(), &ss, nullptr);
+                } else if (search_loads) {
+                    rc = cpd_query_search_loads(ix, &so, 0, nullptr, 0, &ss, nullptr);
                 } else {
                     rc = cpd_query_search(ix, &so, &ss);
                 }
                 if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
                 if (search_paths) write_paths(ix, qfile, s, t, spoff);
+                if (search_loads) write_loads(ix, qfile, g, 1);
                 if (ss.overflow)
                     std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
                                  (unsigned long long)ss.overflow);

@@ -696,6 +696,57 @@ int  cpd_query_search_paths(cpd_index* ix, const cpd_search_opts* opts,
                             uint64_t* offsets /* nq + 1, caller order */,
                             cpd_search_stats* st, cpd_search_paths_info* info);
 
+/* cpd_query_search with the edge loads of every route found — what closes the
+ * traffic-assignment loop of cpd_query_loads / cpd_query_timed: their walk
+ * never depends on the weights, so a second iteration would load the edges
+ * the first did; the route a search finds under cpd_index_set_weights does
+ * react to congestion.  On the queries of the last cpd_query_prepare, for
+ * every query that ends with finished = 1, demand[q] (nq values, the CALLER's
+ * order; NULL = 1 each) is added to the 64-bit counter of each edge of its
+ * route — the route cpd_query_search_paths returns, read when the search has
+ * ended (with its hscale > 1 caveat); finished = 0 or 2 adds nothing.  The
+ * edge of each move, parallel edges told apart (original edge index, as
+ * cpd_query_loads counts):
+ *   prefix move p -> u (u's parent is p in the chain s ... v*): among the
+ *           out-edges of p with head u, the one of least weight under the
+ *           index's current weights, on ties the first in p's out-list (file
+ *           order).  This is the edge whose relaxation set g(u): a relaxation
+ *           scans the out-list in order and replaces g only by a strictly
+ *           smaller value;
+ *   suffix move (the CPD walk from v* to t, lw(v*) moves): the edge the row's
+ *           move names, what cpd_query_loads counts — the edge the reported
+ *           cost was summed over, though a parallel one may be cheaper under
+ *           the current weights.
+ * The table is the index's resident load table, one plane, the kind
+ * cpd_query_loads(nslices = 1) fills: cpd_query_loads_fetch returns its m
+ * values, cpd_query_loads_clear drops it.  flags = 0 makes and zeroes it;
+ * CPD_LOADS_ACCUMULATE adds to a resident one-plane table (none resident: it
+ * starts from zero) — one that cpd_query_loads(nslices = 1) filled too: an
+ * all-or-nothing start, then search iterations; CPD_E_ARG when the resident
+ * table is sliced or a timed walk's, the table stays.  CPD_E_ARG also for
+ * unknown flag bits and for an incomplete index.
+ * Does everything cpd_query_search does (st; cpd_query_fetch and
+ * cpd_query_search_counters afterwards, the oracle's) and, like cpd_query_run,
+ * ends the validity of fetched paths; it builds no node buffer.  The prefix
+ * pool is cpd_query_search_paths' (prefix_bytes, 0 = automatic): when it is
+ * too small the call returns CPD_E_OOM naming the bytes needed, the search's
+ * results are whole and fetchable, the load table is as it was before the
+ * call, and a second call with that many bytes succeeds.  The empty batch is
+ * answered: the table zeroed or kept, info all 0.
+ * The table is carved from the arena as cpd_query_loads' is.                 */
+typedef struct cpd_search_loads_info {
+    uint64_t moves;          /* counter adds made: prefix moves + suffix moves over all routes */
+    uint64_t prefix_moves;   /* ... of them on A*-tree edges                  */
+    uint64_t prefix_nodes;   /* as cpd_search_paths_info                      */
+    uint64_t prefix_bytes;   /* as cpd_search_paths_info                      */
+    double   loads_ms;       /* device time of the two load launches          */
+} cpd_search_loads_info;
+int  cpd_query_search_loads(cpd_index* ix, const cpd_search_opts* opts,
+                            uint64_t prefix_bytes /* 0 = automatic */,
+                            const uint32_t* demand /* nq, caller order; NULL = 1 each */,
+                            uint32_t flags /* 0 | CPD_LOADS_ACCUMULATE */,
+                            cpd_search_stats* st, cpd_search_loads_info* info);
+
 /* ------------------------------------------------------------------------ */
 /* [gpu] Per-kernel device timing (HIP events on the library's stream).      */
 typedef struct cpd_kernel_time {
