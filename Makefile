@@ -26,12 +26,13 @@ LDLIBS    := -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib
 
 HOST_OBJS := $(BLD)/host_util.o $(BLD)/ch.o $(BLD)/ch_gpu.o $(BLD)/plan.o $(BLD)/cpd_io.o \
              $(BLD)/cpd_switches.o $(BLD)/cpd_device.o $(BLD)/cpd_graph.o $(BLD)/cpd_rows.o \
-             $(BLD)/cpd_index.o $(BLD)/cpd_search.o
-DEV_OBJS  := $(BLD)/cpd_kernels.o $(BLD)/ch_kernels.o
+             $(BLD)/cpd_index.o $(BLD)/cpd_search.o $(BLD)/cpd_assign.o
+DEV_OBJS  := $(BLD)/cpd_kernels.o $(BLD)/ch_kernels.o $(BLD)/assign_kernels.o
 TOOLS     := make_cpd_auto fifo_auto gen_distribute_conf gen_synth
 BINS      := $(addprefix bin/,$(TOOLS))
 HDRS      := include/cpd_api.h $(SRC)/cpd_internal.hpp $(SRC)/cpd_kernels.hpp $(SRC)/cpd_io.hpp \
-             $(SRC)/ch_kernels.hpp $(SRC)/cpd_switches.hpp $(SRC)/cpd_gpu_internal.hpp
+             $(SRC)/ch_kernels.hpp $(SRC)/cpd_switches.hpp $(SRC)/cpd_gpu_internal.hpp \
+             $(SRC)/assign_kernels.hpp
 
 # Build provenance: sha256 over the library's and tools' sources (sorted by
 # path, contents concatenated — cpd.src_sha() recomputes it from the shipped
@@ -66,6 +67,9 @@ $(BLD)/cpd_kernels.o: $(SRC)/cpd_kernels.hip $(SRC)/cpd_kernels.hpp $(SRC)/cpd_s
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BLD)/ch_kernels.o: $(SRC)/ch_kernels.hip $(SRC)/ch_kernels.hpp | $(BLD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BLD)/assign_kernels.o: $(SRC)/assign_kernels.hip $(SRC)/assign_kernels.hpp include/cpd_api.h | $(BLD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIB): $(HOST_OBJS) $(DEV_OBJS)

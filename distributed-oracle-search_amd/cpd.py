@@ -62,6 +62,8 @@ EXPORTED = [
     "cpd_index_set_weight_sets", "cpd_query_costs", "cpd_query_costs_fetch",
     "cpd_query_loads", "cpd_query_loads_fetch", "cpd_query_loads_clear", "cpd_query_search_loads",
     "cpd_query_timed", "cpd_query_timed_fetch",
+    "cpd_index_weights_from_loads", "cpd_index_get_weights", "cpd_index_get_weight_sets",
+    "cpd_query_assign",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
@@ -119,6 +121,22 @@ class SearchLoadsInfo(C.Structure):
     _fields_ = [("moves", C.c_uint64), ("prefix_moves", C.c_uint64),
                 ("prefix_nodes", C.c_uint64), ("prefix_bytes", C.c_uint64),
                 ("loads_ms", C.c_double)]
+
+
+class Vdf(C.Structure):
+    _fields_ = [("a_num", C.c_uint32), ("a_den", C.c_uint32), ("power", C.c_uint32),
+                ("load_div", C.c_uint32)]
+
+
+class VdfInfo(C.Structure):
+    _fields_ = [("tstt_lo", C.c_uint64), ("tstt_hi", C.c_uint64), ("changed", C.c_uint64),
+                ("planes", C.c_uint32), ("vdf_ms", C.c_double)]
+
+
+class AssignIter(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("finished", "sptt_lo", "sptt_hi", "tstt_lo", "tstt_hi",
+                                          "moves", "changed")] + \
+               [("search_ms", C.c_double), ("loads_ms", C.c_double), ("vdf_ms", C.c_double)]
 
 
 class KernelTime(C.Structure):
@@ -970,6 +988,92 @@ class Index:
         if nq:
             _check(lib.cpd_query_search_counters(self._h, _ptr(cnt, u32p)))
         return cost, plen, fin, cnt
+
+    def _capacity(self, capacity) -> np.ndarray:
+        c = _u32(capacity)
+        if c.shape != (self.graph.plan.info()["m"],):
+            raise ValueError("capacity must have one entry per edge")
+        return c
+
+    def weights_from_loads(self, capacity, a=(3, 20), power: int = 4, load_div: int = 1) -> dict:
+        """The resident load table turned into weights in HBM
+        (cpd_index_weights_from_loads) by the delay function of cpd_api.h: w' =
+        w0 + w0 * a * (x / c) ** power in integers, x = load // load_div,
+        capacity c one u32 >= 1 per edge (original order).  A one-plane table
+        rewrites the current weights (as set_weights(w') would), K >= 2 planes
+        write weight set j from plane j.  Returns tstt (a Python int: the sum
+        of x * w'), changed, planes, vdf_ms."""
+        c = self._capacity(capacity)
+        f = Vdf(int(a[0]), int(a[1]), int(power), int(load_div))
+        info = VdfInfo()
+        _check(lib.cpd_index_weights_from_loads(self._h, _ptr(c, u32p), C.byref(f),
+                                                C.byref(info)))
+        if info.planes >= 2:
+            self._nsets = info.planes
+        return {"tstt": (info.tstt_hi << 64) | info.tstt_lo, "changed": info.changed,
+                "planes": info.planes, "vdf_ms": info.vdf_ms}
+
+    def get_weights(self) -> np.ndarray:
+        """The current weights, u32[m] in original edge order
+        (cpd_index_get_weights): free flow when none are set."""
+        w = np.empty(self.graph.plan.info()["m"], np.uint32)
+        _check(lib.cpd_index_get_weights(self._h, _ptr(w, u32p)))
+        return w
+
+    def get_weight_sets(self) -> np.ndarray:
+        """The loaded weight sets, u32[nsets, m] (cpd_index_get_weight_sets)."""
+        k = C.c_uint32()
+        _check(lib.cpd_index_get_weight_sets(self._h, C.byref(k), None))
+        w = np.empty((k.value, self.graph.plan.info()["m"]), np.uint32)
+        if k.value:
+            _check(lib.cpd_index_get_weight_sets(self._h, C.byref(k), _ptr(w, u32p)))
+        return w
+
+    def assign(self, s, t, capacity, iters: int, demand=None, a=(3, 20), power: int = 4,
+               **search_opts):
+        """The method of successive averages on the queries (s, t)
+        (cpd_query_assign): `iters` rounds of search_loads under the current
+        weights, then weights_from_loads of the mean loading.  Returns one dict
+        per iteration: finished, sptt and tstt (Python ints), moves, changed,
+        search_ms, loads_ms, vdf_ms.  Afterwards search_fetch() returns the
+        last iteration's search, loads_fetch() the summed loadings and
+        get_weights() the final weights.  search_opts: search_loads' keywords
+        (hscale, fscale, ..., prefix_bytes)."""
+        self.prepare(s, t)
+        return self.assign_run(capacity, iters, demand, a, power, **search_opts)
+
+    def assign_run(self, capacity, iters: int, demand=None, a=(3, 20), power: int = 4,
+                   prefix_bytes=0, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
+                   capacity_cols=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,
+                   capacity_max=0):
+        """cpd_query_assign on the prepared queries (capacity_cols: the
+        search's `capacity` option, renamed beside the edge capacities)."""
+        self._path_offsets = None
+        c = self._capacity(capacity)
+        d = None
+        if demand is not None:
+            d = _u32(demand)
+            if d.shape != (self._nq,):
+                raise ValueError("demand must have one entry per prepared query")
+        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
+                       int(capacity_cols), int(virtual_tick_ns), SEARCH_FORMS[tables],
+                       float(workspace_frac), int(capacity_max))
+        f = Vdf(int(a[0]), int(a[1]), int(power), 1)
+        n = max(0, min(int(iters), 65535))
+        out = (AssignIter * max(1, n))()
+        rc = lib.cpd_query_assign(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)),
+                                  _ptr(d, u32p), _ptr(c, u32p), C.byref(f),
+                                  C.c_uint32(int(iters) & 0xFFFFFFFF), out)
+        if rc == CPD_OK or (rc == CPD_E_OOM and "iteration" in lib.cpd_last_error().decode()):
+            self._load_slices = 1  # a table of the completed iterations is resident
+        _check(rc)
+        recs = []
+        for r in out[:n]:
+            recs.append({"finished": r.finished, "sptt": (r.sptt_hi << 64) | r.sptt_lo,
+                         "tstt": (r.tstt_hi << 64) | r.tstt_lo, "moves": r.moves,
+                         "changed": r.changed, "search_ms": r.search_ms,
+                         "loads_ms": r.loads_ms, "vdf_ms": r.vdf_ms})
+        return recs
 
     def __del__(self):
         if getattr(self, "_h", None):

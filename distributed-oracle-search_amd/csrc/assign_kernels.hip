@@ -1,0 +1,204 @@
+// gfx950 kernels of the assignment loop (cpd_index_weights_from_loads,
+// cpd_index_get_weights, cpd_query_assign): everything is slot-wise over
+// tables already in HBM in one layout — the load table, the free-flow
+// adjacency, the selected adjacency and the weight-set records all index a
+// slot as (column << shift) + move — so no kernel here permutes anything but
+// the capacities in and the weights out.
+#include <hip/hip_runtime.h>
+
+#include "assign_kernels.hpp"
+
+namespace cpd {
+namespace kern {
+
+// A 128-bit unsigned sum kept as two u64 halves.
+struct U128 {
+    unsigned long long lo, hi;
+};
+
+__device__ __forceinline__ void add128(U128& a, unsigned long long lo, unsigned long long hi) {
+    a.lo += lo;
+    a.hi += hi + (a.lo < lo ? 1ull : 0ull);
+}
+
+// a += x * y, the product's high half from __umul64hi
+__device__ __forceinline__ void mad128(U128& a, unsigned long long x, unsigned long long y) {
+    add128(a, x * y, __umul64hi(x, y));
+}
+
+// The wave's sum in lane 0, then into acc[0] (low) and acc[1] (high): the low
+// add's returned old value shows whether it wrapped, and the wrap is carried
+// into the high half.  Every add commutes, so the total is exact whatever the
+// order the waves arrive in.  cnt goes to acc[2] the same way.
+__device__ __forceinline__ void wave_sum128(U128 a, unsigned long long cnt,
+                                            unsigned long long* __restrict__ acc) {
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long lo = __shfl_down(a.lo, d, 64);
+        const unsigned long long hi = __shfl_down(a.hi, d, 64);
+        add128(a, lo, hi);
+        cnt += __shfl_down(cnt, d, 64);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        unsigned long long hi = a.hi;
+        if (a.lo) {
+            const unsigned long long old = atomicAdd(&acc[0], a.lo);
+            if (old + a.lo < old) ++hi;
+        }
+        if (hi) atomicAdd(&acc[1], hi);
+        if (cnt) atomicAdd(&acc[2], cnt);
+    }
+}
+
+// The delay function (cpd_api.h): w' of a slot with free-flow weight w0,
+// capacity c >= 1 and volume x = counter / load_div.  Every intermediate fits
+// 64 bits: r <= 2^20, p <= 2^32, w0 * p < 2^64, t < 2^48, t * a_num < 2^64.
+__device__ __forceinline__ uint32_t vdf_weight(uint32_t w0, unsigned long long x, uint32_t c,
+                                               const cpd_vdf& f) {
+    if (x == 0ull) return w0;  // r = 0: nothing is added
+    const unsigned long long r =
+        x >= ((unsigned long long)c << 4) ? (1ull << 20) : (x << 16) / c;
+    unsigned long long p = r;
+    for (uint32_t i = 1; i < f.power; ++i) p = (p * r) >> 16;
+    const unsigned long long t = ((unsigned long long)w0 * p) >> 16;
+    const unsigned long long add = t * f.a_num / f.a_den;
+    return add >= 0xFFFFFFFFull - w0 ? 0xFFFFFFFFu : w0 + (uint32_t)add;
+}
+
+__global__ __launch_bounds__(256) void capacity_scatter(const uint32_t* __restrict__ capacity,
+                                                        const uint32_t* __restrict__ slot_of_edge,
+                                                        uint32_t m, uint32_t* __restrict__ cap_slot) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < m) cap_slot[slot_of_edge[e]] = capacity[e];
+}
+
+// A lane per slot, grid-stride; KW = 0: the one-plane form into the selected
+// adjacency, KW = 4 / 8: a weight-set record per slot and the closing record
+// of zeros (slot index nslots).
+template <uint32_t KW>
+__global__ __launch_bounds__(256) void vdf_update(const unsigned long long* __restrict__ tab,
+                                                  const uint2* __restrict__ adj_free,
+                                                  const uint32_t* __restrict__ cap_slot,
+                                                  unsigned long long nslots, uint32_t planes,
+                                                  cpd_vdf f, uint2* __restrict__ adj_out,
+                                                  uint4* __restrict__ wsets,
+                                                  unsigned long long* __restrict__ acc) {
+    U128 sum{0ull, 0ull};
+    unsigned long long changed = 0;
+    const unsigned long long end = KW ? nslots + 1ull : nslots;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < end;
+         i += step) {
+        uint32_t rec[KW ? KW : 1];
+#pragma unroll
+        for (uint32_t j = 0; j < (KW ? KW : 1u); ++j) rec[j] = 0u;
+        uint2 a = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+        if (i < nslots) a = adj_free[i];
+        if (a.x != 0xFFFFFFFFu) {  // a real edge: padding slots keep their record
+            const uint32_t c = cap_slot[i];
+#pragma unroll
+            for (uint32_t j = 0; j < (KW ? KW : 1u); ++j) {
+                if (j >= planes) break;
+                unsigned long long x = tab[(unsigned long long)j * nslots + i];
+                if (f.load_div > 1u) x /= f.load_div;
+                const uint32_t w = vdf_weight(a.y, x, c, f);
+                rec[j] = w;
+                mad128(sum, x, w);
+                changed += w != a.y ? 1ull : 0ull;
+            }
+        }
+        if constexpr (KW == 0u) {
+            if (a.x != 0xFFFFFFFFu) a.y = rec[0];
+            adj_out[i] = a;
+        } else {
+#pragma unroll
+            for (uint32_t q = 0; q < KW / 4u; ++q)
+                wsets[i * (KW / 4u) + q] =
+                    make_uint4(rec[4u * q], rec[4u * q + 1u], rec[4u * q + 2u], rec[4u * q + 3u]);
+        }
+    }
+    wave_sum128(sum, changed, acc);
+}
+
+__global__ __launch_bounds__(256) void weights_gather(const uint32_t* __restrict__ src,
+                                                      const uint32_t* __restrict__ slot_of_edge,
+                                                      uint32_t m, uint32_t stride, uint32_t first,
+                                                      uint32_t cols, uint32_t* __restrict__ out) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (unsigned long long)m * cols) return;
+    const uint32_t j = (uint32_t)(i / m), e = (uint32_t)(i - (unsigned long long)j * m);
+    out[i] = src[(unsigned long long)slot_of_edge[e] * stride + first + j];
+}
+
+__global__ __launch_bounds__(256) void sptt_reduce(const unsigned long long* __restrict__ cost,
+                                                   const uint8_t* __restrict__ fin,
+                                                   const uint32_t* __restrict__ qperm,
+                                                   const uint32_t* __restrict__ demand, uint32_t nq,
+                                                   unsigned long long* __restrict__ acc) {
+    U128 sum{0ull, 0ull};
+    unsigned long long finished = 0;
+    const uint32_t step = gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq;
+         i += step) {
+        if (fin[i] != 1u) continue;
+        const unsigned long long d = demand ? demand[qperm[i]] : 1ull;
+        mad128(sum, d, cost[i]);
+        ++finished;
+    }
+    wave_sum128(sum, finished, acc);
+}
+
+}  // namespace kern
+
+namespace {
+// grid-stride launches: enough workgroups of 256 to fill the device, no more
+uint32_t stride_grid(unsigned long long items) {
+    const unsigned long long blocks = (items + 255ull) / 256ull;
+    return (uint32_t)(blocks < 1ull ? 1ull : blocks > 4096ull ? 4096ull : blocks);
+}
+}  // namespace
+
+void launch_capacity_scatter(const uint32_t* capacity, const uint32_t* slot_of_edge, uint32_t m,
+                             uint32_t* cap_slot, hipStream_t s) {
+    if (!m) return;
+    hipLaunchKernelGGL(kern::capacity_scatter, dim3((m + 255u) / 256u), dim3(256), 0, s, capacity,
+                       slot_of_edge, m, cap_slot);
+}
+
+void launch_vdf_update(const uint64_t* tab, const uint32_t* adj_free, const uint32_t* cap_slot,
+                       uint64_t nslots, uint32_t planes, cpd_vdf f, uint32_t set_words,
+                       uint32_t* adj_out, uint32_t* wsets, unsigned long long* acc, hipStream_t s) {
+    const auto* t = reinterpret_cast<const unsigned long long*>(tab);
+    const auto* af = reinterpret_cast<const uint2*>(adj_free);
+    auto* ao = reinterpret_cast<uint2*>(adj_out);
+    auto* ws = reinterpret_cast<uint4*>(wsets);
+    const dim3 grid(stride_grid(nslots + 1ull)), blk(256);
+    if (set_words == 0u)
+        hipLaunchKernelGGL(kern::vdf_update<0>, grid, blk, 0, s, t, af, cap_slot, nslots, planes, f,
+                           ao, ws, acc);
+    else if (set_words == 4u)
+        hipLaunchKernelGGL(kern::vdf_update<4>, grid, blk, 0, s, t, af, cap_slot, nslots, planes, f,
+                           ao, ws, acc);
+    else
+        hipLaunchKernelGGL(kern::vdf_update<8>, grid, blk, 0, s, t, af, cap_slot, nslots, planes, f,
+                           ao, ws, acc);
+}
+
+void launch_weights_gather(const uint32_t* src, const uint32_t* slot_of_edge, uint32_t m,
+                           uint32_t stride, uint32_t first, uint32_t cols, uint32_t* out,
+                           hipStream_t s) {
+    const unsigned long long total = (unsigned long long)m * cols;
+    if (!total) return;
+    hipLaunchKernelGGL(kern::weights_gather, dim3((uint32_t)((total + 255ull) / 256ull)), dim3(256),
+                       0, s, src, slot_of_edge, m, stride, first, cols, out);
+}
+
+void launch_sptt_reduce(const uint64_t* cost, const uint8_t* fin, const uint32_t* qperm,
+                        const uint32_t* demand, uint32_t nq, unsigned long long* acc,
+                        hipStream_t s) {
+    if (!nq) return;
+    hipLaunchKernelGGL(kern::sptt_reduce, dim3(stride_grid(nq)), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long*>(cost), fin, qperm, demand, nq,
+                       acc);
+}
+
+}  // namespace cpd

@@ -1,0 +1,51 @@
+// Host-callable launchers for the gfx950 kernels in assign_kernels.hip: the
+// slot-wise step from edge loads to weights (cpd_index_weights_from_loads),
+// the weights' way back to edge order (cpd_index_get_weights / _weight_sets)
+// and the demand-weighted cost sum of a search (cpd_query_assign).
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <cstdint>
+
+#include "cpd_api.h"
+
+namespace cpd {
+
+// cap_slot[slot_of_edge[e]] = capacity[e] for the m edges: the capacities in
+// the load table's adjacency-slot order.  Slots past a column's out-degree
+// are not written (the update never reads them).
+void launch_capacity_scatter(const uint32_t* capacity, const uint32_t* slot_of_edge, uint32_t m,
+                             uint32_t* cap_slot, hipStream_t s);
+
+// The delay function of cpd_api.h ("The delay function") over every slot of
+// `planes` planes of the load table tab (planes x nslots u64, nslots = n <<
+// shift), from the free-flow adjacency adj_free ((dst, w0) per slot) and the
+// slot-order capacities:
+//   set_words == 0: one plane; adj_out (2 x nslots u32) gets (dst, w') per
+//       slot, padding slots (dst 0xFFFFFFFF) copied from adj_free;
+//   set_words == 4 or 8 (weight_set_words(planes)): wsets gets one record of
+//       set_words u32 per slot, word j = w' of plane j, zeros past `planes`
+//       and in padding slots, and the record of zeros after the last slot
+//       (nslots + 1 records): the table launch_table_costs reads.
+// acc[0], acc[1] += the low and high half of the sum of x * w' over the real
+// slots of every plane (128-bit, carries exact: adds commute), acc[2] += the
+// (plane, slot) pairs with w' != w0; the caller zeroes acc.
+void launch_vdf_update(const uint64_t* tab, const uint32_t* adj_free, const uint32_t* cap_slot,
+                       uint64_t nslots, uint32_t planes, cpd_vdf f, uint32_t set_words,
+                       uint32_t* adj_out, uint32_t* wsets, unsigned long long* acc, hipStream_t s);
+
+// out[j * m + e] = src[slot_of_edge[e] * stride + first + j], j < cols: the
+// weights of a packed adjacency (stride 2, first 1, cols 1) or of a set table
+// (stride = its record's words, first 0, cols = the sets) in edge order.
+void launch_weights_gather(const uint32_t* src, const uint32_t* slot_of_edge, uint32_t m,
+                           uint32_t stride, uint32_t first, uint32_t cols, uint32_t* out,
+                           hipStream_t s);
+
+// Over the nq sorted queries of a search (cost / fin as the search kernel left
+// them, qperm[i] = the caller's index of sorted query i): acc[0], acc[1] += the
+// 128-bit sum of demand[qperm[i]] (NULL: 1) * cost[i] over the queries with
+// fin == 1, acc[2] += their number; the caller zeroes acc.
+void launch_sptt_reduce(const uint64_t* cost, const uint8_t* fin, const uint32_t* qperm,
+                        const uint32_t* demand, uint32_t nq, unsigned long long* acc,
+                        hipStream_t s);
+
+}  // namespace cpd

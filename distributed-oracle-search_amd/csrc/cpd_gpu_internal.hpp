@@ -533,6 +533,12 @@ struct cpd_index {
     DevBuf<uint32_t> spp_pool, spp_pn, spp_vcol, spp_vlw, spp_wperm;
     DevBuf<unsigned long long> spp_top, spp_off;
     DevBuf<uint64_t> spp_woff;
+    // loads to weights (cpd_index_weights_from_loads, cpd_query_assign): the
+    // call's capacities as uploaded (edge order) and permuted to slot order,
+    // the 128-bit sum and the changed count; the edge-order copy of a weights
+    // fetch (cpd_index_get_weights / _weight_sets).  Carved like ld_tab.
+    DevBuf<uint32_t> vdf_cap_in, vdf_cap, vdf_out;
+    DevBuf<unsigned long long> vdf_acc;
 };
 
 template <class F>
@@ -583,4 +589,5 @@ void fold_late(cpd_graph* g, size_t keep);  // cpd_rows.cpp
 void ensure_dense(cpd_index* ix);           // cpd_index.cpp
 void reset_load_table(cpd_index* ix, uint32_t planes, uint32_t slice_moves,
                       uint64_t period);     // cpd_index.cpp
+void ensure_slot_of_edge(cpd_graph* g);     // cpd_index.cpp
 }  // namespace cpd

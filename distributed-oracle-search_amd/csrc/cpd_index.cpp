@@ -560,10 +560,12 @@ double run_walk(cpd_index* ix, int32_t k_moves, cpd_query_stats* st) {
     return bytes;
 }
 
+}  // namespace
+
 // The load table's fetch order (edge loads, timed walks; at first use):
 // column-space edge ec of column c sits in slot c * stride + its place in c's
 // out-list; edge_perm names its file edge.
-void ensure_slot_of_edge(cpd_graph* g) {
+void cpd::ensure_slot_of_edge(cpd_graph* g) {
     if (g->slot_of_edge_d.p) return;
     const size_t stride = (size_t)1 << g->adj_shift;
     std::vector<uint32_t> soe(g->m);
@@ -573,8 +575,6 @@ void ensure_slot_of_edge(cpd_graph* g) {
     g->slot_of_edge_d.upload(soe.data(), soe.size(), g->stream);
     HIP_CHECK(hipStreamSynchronize(g->stream));  // soe leaves scope
 }
-
-}  // namespace
 
 // The resident load table made again: `planes` zeroed planes of the kind given
 // (slice_moves and period as cpd_index keeps them), from the arena when one is

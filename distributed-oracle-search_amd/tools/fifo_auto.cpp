@@ -14,6 +14,8 @@
 //                                           only: also write every edge's load)
 //             [--timed P [--loads]]  (table-search only: cost, and load, every
 //                                     move under the diff of its clock time)
+//             [--assign K --capacity C [--vdf A/B^P]]  (cpd-search only: K
+//                                     iterations of load and re-weight)
 //             [--verbose]  (per request on stderr: read+parse / prepare / compute)
 //
 // Creates its request FIFO, streams the CPD buckets this worker owns onto its
@@ -84,6 +86,22 @@
 // well the call carries CPD_TIMED_LOADS (demand 1 per query line, not
 // accumulated across requests) and <query file>.loads holds the loaded edges
 // in the format above, one column per diff.  The answer line keeps its fields.
+// With --assign K --capacity C (cpd-search only; not with --search-paths,
+// --search-loads, --loads or --timed) every request is answered through
+// cpd_query_assign: K iterations (1..65535) of cpd_query_search_loads at a
+// demand of 1 per query line and cpd_index_weights_from_loads of the mean
+// loading, started from the request's diff, every edge at the uniform capacity
+// C (1 <= C < 2^32; per-edge capacities are for the ABI) under the delay
+// function --vdf A/B^P (default 3/20^4: w' = w0 (1 + A/B (x / C)^P), cpd_api.h
+// "The delay function").  The answer line and <query file>.res are the last
+// iteration's search.  <query file>.loads holds the summed loadings in the
+// format of --loads with one column; <query file>.assign one line per
+// iteration, "k finished sptt tstt moves changed" (sptt and tstt in decimal,
+// up to 39 digits); <query file>.diff the final weights as "e from to cost"
+// lines for the edges that differ from the .xy file's (each written as .tmp
+// and renamed into place).  A .diff names an edge by its endpoints, so of
+// parallel edges only the first can be re-weighted by it.  Every request
+// starts again from its diff: nothing is carried from one request to the next.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -251,6 +269,42 @@ static void write_loads(cpd_index* ix, const std::string& qfile, const cpd::io::
     }
 }
 
+// a 128-bit unsigned value in decimal
+static std::string dec128(uint64_t lo, uint64_t hi) {
+    unsigned __int128 v = ((unsigned __int128)hi << 64) | lo;
+    std::string d;
+    do d.insert(d.begin(), (char)('0' + (int)(v % 10u))); while (v /= 10u);
+    return d;
+}
+
+// <query file>.assign and <query file>.diff of an --assign request
+static void write_assign(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g,
+                         const std::vector<cpd_assign_iter>& it) {
+    std::string path = qfile + ".assign", tmp = path + ".tmp";
+    std::FILE* f = std::fopen(tmp.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    bool ok = true;
+    for (size_t k = 0; k < it.size() && ok; ++k)
+        ok = std::fprintf(f, "%zu %llu %s %s %llu %llu\n", k + 1, (unsigned long long)it[k].finished,
+                          dec128(it[k].sptt_lo, it[k].sptt_hi).c_str(),
+                          dec128(it[k].tstt_lo, it[k].tstt_hi).c_str(),
+                          (unsigned long long)it[k].moves, (unsigned long long)it[k].changed) > 0;
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
+        ::unlink(tmp.c_str());
+        throw std::runtime_error("cannot write " + path);
+    }
+    std::vector<uint32_t> w(g.m);
+    if (cpd_index_get_weights(ix, w.data()) != CPD_OK) throw std::runtime_error(cpd_last_error());
+    path = qfile + ".diff";
+    tmp = path + ".tmp";
+    cpd::io::write_diff(tmp, g, w);
+    if (::rename(tmp.c_str(), path.c_str()) != 0) {
+        ::unlink(tmp.c_str());
+        throw std::runtime_error("cannot write " + path);
+    }
+}
+
 // <query file>.dep of a --timed request: one unsigned integer per query line;
 // no such file: every query leaves at 0 (dep stays empty)
 static void read_departures(const std::string& qfile, size_t nq, std::vector<uint64_t>& dep) {
@@ -390,7 +444,15 @@ int main(int argc, char** argv) {
                      "                  line; absent: 0); <query file>.res gets, per query:\n"
                      "                  s t moves finished depart cost\n"
                      "                  (with --loads <query file>.loads has one column per "
-                     "diff)\n");
+                     "diff)\n"
+                     "       [--assign K --capacity C [--vdf A/B^P]]  cpd-search only: answer "
+                     "through\n"
+                     "                  cpd_query_assign (K iterations, demand 1 per query, every "
+                     "edge at capacity C,\n"
+                     "                  delay w0 (1 + A/B (x/C)^P), default 3/20^4); writes <query "
+                     "file>.loads,\n"
+                     "                  .assign (k finished sptt tstt moves changed) and .diff (the "
+                     "final weights)\n");
         return 2;
     }
     // table-search (make_fifos.py:20) or the CPD-heuristic search
@@ -461,6 +523,33 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "fifo_auto: --load-slices K --load-slice-moves S need --loads, 2 <= K "
                              "<= %u and 0 < S < 2^32 (both or neither)\n", CPD_MAX_LOAD_SLICES);
         return 2;
+    }
+    const bool assign = a.has("assign");
+    if (assign && (!search || search_paths || search_loads || loads || timed)) {
+        std::fprintf(stderr, "fifo_auto: --assign needs --alg cpd-search without --search-paths, "
+                             "--search-loads, --loads or --timed (the loop answers through "
+                             "cpd_query_assign and writes the loads itself)\n");
+        return 2;
+    }
+    const long long assign_iters = a.num("assign", 0), assign_cap = a.num("capacity", 0);
+    cpd_vdf vdf{3, 20, 4, 1};
+    {
+        const std::string v = a.str("vdf", "3/20^4");
+        unsigned an = 0, ad = 0, pw = 0;
+        char tail = 0;
+        const bool ok = std::sscanf(v.c_str(), "%u/%u^%u%c", &an, &ad, &pw, &tail) == 3 &&
+                        an <= 65535u && ad >= 1u && ad <= 65535u && pw >= 1u && pw <= 4u;
+        if ((a.has("vdf") || a.has("capacity")) && !assign) {
+            std::fprintf(stderr, "fifo_auto: --capacity and --vdf need --assign\n");
+            return 2;
+        }
+        if (assign && (!ok || assign_iters < 1 || assign_iters > 65535 || assign_cap < 1 ||
+                       assign_cap > 0xFFFFFFFFll)) {
+            std::fprintf(stderr, "fifo_auto: --assign K --capacity C [--vdf A/B^P] need 1 <= K <= "
+                                 "65535, 1 <= C < 2^32, A <= 65535, 1 <= B <= 65535 and 1 <= P <= 4\n");
+            return 2;
+        }
+        vdf = cpd_vdf{an, ad, pw, 1};
     }
     int mcode = cli::method_code(method);
     std::string xy = inputs[0];
@@ -772,7 +861,39 @@ int main(int argc, char** argv) {
             double t_receive = now() - t0;
             cpd_query_stats st{};
             cpd_search_stats ss{};
-            if (search) {
+            if (assign) {
+                // the loop leaves w_{K+1} on the index: the next request sets
+                // its diff's weights again, whatever its name
+                active_diff.clear();
+                static std::vector<uint32_t> cap;
+                cap.assign(g.m, (uint32_t)assign_cap);
+                std::vector<cpd_assign_iter> it((size_t)assign_iters);
+                rc = cpd_query_assign(ix, &so, 0, nullptr, cap.data(), &vdf, (uint32_t)assign_iters,
+                                      it.data());
+                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                write_loads(ix, qfile, g, 1);
+                write_assign(ix, qfile, g, it);
+                // the answer line's sums, from the last iteration's search
+                std::vector<uint32_t> cnt(5 * nq), plen(nq);
+                std::vector<uint8_t> fin(nq);
+                if (nq) cli::check(cpd_query_search_counters(ix, cnt.data()), "counters");
+                cli::check(cpd_query_fetch(ix, nullptr, plen.data(), fin.data()), "fetch");
+                uint64_t* sums[5] = {&ss.expanded, &ss.inserted, &ss.touched, &ss.updated, &ss.surplus};
+                for (size_t q = 0; q < nq; ++q) {
+                    for (int k = 0; k < 5; ++k) *sums[k] += cnt[5 * q + k];
+                    if (fin[q] == 1) {
+                        ss.plen += plen[q];
+                        ss.finished++;
+                    } else if (fin[q] == 2) {
+                        ss.overflow++;
+                    }
+                }
+                ss.kernel_ms = ss.tables_ms = 0.0;
+                for (const auto& r : it) ss.kernel_ms += r.search_ms;  // tables included
+                if (ss.overflow)
+                    std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
+                                 (unsigned long long)ss.overflow);
+            } else if (search) {
                 static std::vector<uint64_t> spoff;
                 if (search_paths) {
                     spoff.resize(nq + 1);

@@ -748,6 +748,124 @@ int  cpd_query_search_loads(cpd_index* ix, const cpd_search_opts* opts,
                             cpd_search_stats* st, cpd_search_loads_info* info);
 
 /* ------------------------------------------------------------------------ */
+/* [gpu] The assignment loop — loads to weights in HBM, iterated with
+ * cpd-search.  cpd_query_loads / cpd_query_timed / cpd_query_search_loads
+ * leave edge loads in the index's resident table; the step below turns them
+ * into weights without leaving HBM (the load table, the free-flow adjacency,
+ * the selected adjacency and the weight-set table all index an adjacency slot
+ * the same way, so the update is slot-wise: no permutation, no host copy),
+ * and cpd_query_assign iterates search, load and update.  The reference takes
+ * its congestion `diffs` as given (process_query.py:178); nothing in it makes
+ * them.
+ *
+ * The delay function.  Integer arithmetic, every intermediate fits 64 bits.
+ * For an edge with free-flow weight w0, capacity c >= 1 and load counter L:
+ *     x   = L / load_div
+ *     r   = (x >= ((u64)c << 4)) ? (1 << 20) : ((x << 16) / c)
+ *                                   the ratio x / c in Q16, clamped at 16.0
+ *     p   = r;  repeat power - 1 times:  p = (p * r) >> 16        p <= 2^32
+ *     t   = (w0 * p) >> 16
+ *     add = (t * a_num) / a_den
+ *     w'  = min(w0 + add, 0xFFFFFFFF)   in mathematical integers: the sum is
+ *                                        never allowed to wrap
+ * All divisions truncate.  w0 is always the FREE-FLOW weight, never the
+ * current one: the update does not compound.  L = 0 gives w' = w0, and w' >=
+ * w0 always, so the search's heuristic stays consistent for hscale <= 1.
+ * Adjacency slots past a column's out-degree are copied unchanged: a move
+ * that names no out-edge still stops a walk.  BPR is a = 3/20, power 4;
+ * load_div is the number of all-or-nothing loadings the counters sum (x =
+ * their mean). */
+typedef struct cpd_vdf {
+    uint32_t a_num;    /* 0..65535 */
+    uint32_t a_den;    /* 1..65535 */
+    uint32_t power;    /* 1..4 */
+    uint32_t load_div; /* >= 1 */
+} cpd_vdf;
+
+typedef struct cpd_vdf_info {
+    uint64_t tstt_lo, tstt_hi; /* sum over edges and planes of x * w', 128 bits (mod 2^128) */
+    uint64_t changed;          /* (plane, edge) pairs with w' != w0 */
+    uint32_t planes;           /* planes of the table read */
+    double   vdf_ms;           /* device time of the capacity permutation + the update */
+} cpd_vdf_info;
+
+/* Weights from the resident load table.  capacity: m values in original edge
+ * order, each >= 1.  What is written depends on the table's kind:
+ *   one plane (cpd_query_loads with nslices = 1, cpd_query_search_loads): the
+ *       index's CURRENT weights, w' on every edge — the state
+ *       cpd_index_set_weights(w') leaves (the search's incumbent tables are
+ *       rebuilt at the next search); cpd_index_set_weights(ix, NULL) still
+ *       restores free flow;
+ *   K >= 2 planes (sliced cpd_query_loads, cpd_query_timed with
+ *       CPD_TIMED_LOADS): weight set j from plane j, K sets, as
+ *       cpd_index_set_weight_sets(K, ..) would hold them; the current weights
+ *       and the search's tables are left as they were.
+ * The load table is only read.  The update and the 128-bit sum are one kernel
+ * pass over the slots; integer adds commute, so info is exact and the same in
+ * every run.  The capacities are uploaded and permuted to slot order by a
+ * small kernel on every call (4 m bytes; no copy is kept between calls, so a
+ * caller may change them freely).
+ * CPD_E_ARG, naming the first offending value: no resident table, an
+ * incomplete index, capacity NULL or some capacity 0, a_num > 65535, a_den or
+ * power out of range, load_div 0.  On error the table, the weights and the
+ * sets are untouched.  info may be NULL.  The buffers are carved from the
+ * arena as the load table is.                                                */
+int  cpd_index_weights_from_loads(cpd_index* ix, const uint32_t* capacity /* m, edge order, >= 1 */,
+                                  const cpd_vdf* f, cpd_vdf_info* info);
+/* The index's current weights in original edge order (m values): what
+ * cpd_index_set_weights was given or cpd_index_weights_from_loads wrote, the
+ * free-flow weights when no custom weights are set.  Permuted from slot order
+ * on the GPU and copied out once, as cpd_query_loads_fetch does.  With
+ * parallel edges told apart, as everywhere in this header.                   */
+int  cpd_index_get_weights(cpd_index* ix, uint32_t* w /* m, edge order */);
+/* The loaded weight sets: *nsets, and when w != NULL set j at w[j * m + e]
+ * (*nsets * m values; call with w == NULL first to size it).                */
+int  cpd_index_get_weight_sets(cpd_index* ix, uint32_t* nsets, uint32_t* w /* nsets * m, may be NULL */);
+
+/* The method of successive averages over the queries of the last
+ * cpd_query_prepare.  Iteration k = 1 .. iters:
+ *   1. cpd_query_search_loads(opts, prefix_bytes, demand, k == 1 ? 0 :
+ *      CPD_LOADS_ACCUMULATE): an all-or-nothing loading under the current
+ *      weights w_k, summed into the resident table;
+ *   2. sptt_k = sum over the queries with finished == 1 of demand[q] *
+ *      cost[q] (128 bits), the cost being the one found under w_k;
+ *   3. cpd_index_weights_from_loads with load_div = k (f->load_div is
+ *      ignored): x_k = the mean of the k loadings, w_{k+1} from it, and
+ *      tstt_k = x_k . w_{k+1}.
+ * Iteration 1 searches under the index's current weights (a caller can warm
+ * start); the update after the last iteration is still made, so the index
+ * ends with w_{iters+1}.  The relative gap of step k is formed by the CALLER
+ * from record k's tstt and record k+1's sptt — (tstt_k - sptt_{k+1}) /
+ * tstt_k, both under w_{k+1}; the last record has no such partner.
+ * Afterwards cpd_query_fetch and cpd_query_search_counters return the last
+ * iteration's search and cpd_query_loads_fetch the summed table (iters times
+ * the mean).  The prefix pool's CPD_E_OOM of cpd_query_search_loads passes
+ * through from iteration 1 with nothing changed; in a later iteration the
+ * call stops there — the message names the iteration — with the table and
+ * weights of the iterations that completed (their records are filled, the
+ * others zero).  The empty batch is answered: all-zero records, a zeroed
+ * table, w0 on every edge.  opts->time_ns without virtual_tick_ns is a wall
+ * clock limit, honoured as cpd_query_search honours it: such a loop is not
+ * reproducible.  CPD_E_ARG for iters outside 1..65535, a NULL out or
+ * capacity, a capacity of 0, f out of range, an incomplete index.
+ * Out of scope: a demand set larger than one prepared batch (write the loop
+ * from cpd_query_search_loads(CPD_LOADS_ACCUMULATE) and
+ * cpd_index_weights_from_loads(load_div), which is why both are public); a
+ * time-dependent search; line search, Frank-Wolfe and other step rules.     */
+typedef struct cpd_assign_iter {
+    uint64_t finished;          /* queries with finished == 1 in this iteration  */
+    uint64_t sptt_lo, sptt_hi;  /* sum over those of demand[q] * cost[q], under the weights searched with */
+    uint64_t tstt_lo, tstt_hi;  /* this iteration's cpd_vdf_info sum: x_k . w_{k+1} */
+    uint64_t moves, changed;    /* counter adds of the loading; edges with w_{k+1} != w0 */
+    double   search_ms, loads_ms, vdf_ms;
+} cpd_assign_iter;
+int  cpd_query_assign(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                      const uint32_t* demand /* nq, caller order; NULL = 1 each */,
+                      const uint32_t* capacity /* m, edge order, >= 1 */,
+                      const cpd_vdf* f /* load_div ignored */, uint32_t iters /* 1..65535 */,
+                      cpd_assign_iter* out /* iters records */);
+
+/* ------------------------------------------------------------------------ */
 /* [gpu] Per-kernel device timing (HIP events on the library's stream).      */
 typedef struct cpd_kernel_time {
     char     name[32];
