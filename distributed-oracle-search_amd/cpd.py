@@ -38,6 +38,7 @@ MAX_WEIGHT_SETS = 8
 MAX_LOAD_SLICES = 8
 LOADS_ACCUMULATE = 1
 TIMED_LOADS = 2
+STEP_LINE = 0xFFFFFFFF
 
 EXPORTED = [
     "cpd_last_error", "cpd_version", "cpd_partition", "cpd_partition_nbuckets",
@@ -64,6 +65,7 @@ EXPORTED = [
     "cpd_query_timed", "cpd_query_timed_fetch",
     "cpd_index_weights_from_loads", "cpd_index_get_weights", "cpd_index_get_weight_sets",
     "cpd_query_assign",
+    "cpd_index_flow_step", "cpd_index_flow_fetch", "cpd_index_flow_clear", "cpd_query_assign_line",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
@@ -137,6 +139,25 @@ class AssignIter(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("finished", "sptt_lo", "sptt_hi", "tstt_lo", "tstt_hi",
                                           "moves", "changed")] + \
                [("search_ms", C.c_double), ("loads_ms", C.c_double), ("vdf_ms", C.c_double)]
+
+
+class FlowInfo(C.Structure):
+    _fields_ = [("lambda_q16", C.c_uint32), ("evals", C.c_uint32)] + \
+               [(k, C.c_uint64) for k in ("g0_lo", "g0_hi", "xw0_lo", "xw0_hi", "tstt_lo",
+                                          "tstt_hi", "changed")] + \
+               [("line_ms", C.c_double), ("apply_ms", C.c_double)]
+
+
+class AssignLineIter(C.Structure):
+    _fields_ = AssignIter._fields_ + [("lambda_q16", C.c_uint32), ("evals", C.c_uint32)] + \
+               [(k, C.c_uint64) for k in ("g0_lo", "g0_hi", "xw0_lo", "xw0_hi")] + \
+               [("line_ms", C.c_double)]
+
+
+def _s128(lo: int, hi: int) -> int:
+    """A signed 128-bit value from its two u64 halves."""
+    v = (hi << 64) | lo
+    return v - (1 << 128) if hi >> 63 else v
 
 
 class KernelTime(C.Structure):
@@ -1073,6 +1094,86 @@ class Index:
                          "tstt": (r.tstt_hi << 64) | r.tstt_lo, "moves": r.moves,
                          "changed": r.changed, "search_ms": r.search_ms,
                          "loads_ms": r.loads_ms, "vdf_ms": r.vdf_ms})
+        return recs
+
+    @staticmethod
+    def _lambda(lam) -> int:
+        return STEP_LINE if lam == "line" else int(lam) & 0xFFFFFFFF
+
+    def flow_step(self, capacity, lam="line", a=(3, 20), power: int = 4) -> dict:
+        """One flow step towards the resident one-plane load table
+        (cpd_index_flow_step, cpd_api.h "The flow step"): lam = "line" for the
+        line rule or a step in 0..65536 (Q16).  Without a flow table the step
+        initialises it from the loads.  Returns lambda_q16, evals, g0 (a signed
+        Python int), xw0 and tstt (Python ints), changed, line_ms, apply_ms;
+        the relative gap before the step is -g0 / xw0."""
+        c = self._capacity(capacity)
+        f = Vdf(int(a[0]), int(a[1]), int(power), 1)
+        info = FlowInfo()
+        _check(lib.cpd_index_flow_step(self._h, _ptr(c, u32p), C.byref(f),
+                                       C.c_uint32(self._lambda(lam)), C.byref(info)))
+        return {"lambda_q16": info.lambda_q16, "evals": info.evals,
+                "g0": _s128(info.g0_lo, info.g0_hi), "xw0": (info.xw0_hi << 64) | info.xw0_lo,
+                "tstt": (info.tstt_hi << 64) | info.tstt_lo, "changed": info.changed,
+                "line_ms": info.line_ms, "apply_ms": info.apply_ms}
+
+    def flow_fetch(self) -> np.ndarray:
+        """The flow table, u64[m] in original edge order, Q16
+        (cpd_index_flow_fetch): the volume of edge e is flow[e] >> 16."""
+        x = np.empty(self.graph.plan.info()["m"], np.uint64)
+        _check(lib.cpd_index_flow_fetch(self._h, _ptr(x, u64p)))
+        return x
+
+    def flow_clear(self) -> None:
+        """Drop the flow table (cpd_index_flow_clear)."""
+        _check(lib.cpd_index_flow_clear(self._h))
+
+    def assign_line(self, s, t, capacity, iters: int, demand=None, a=(3, 20), power: int = 4,
+                    **search_opts):
+        """assign() with the line-search step (cpd_query_assign_line): one dict
+        per iteration made — the loop stops early after an iteration k >= 2
+        with lambda 0 — holding assign()'s keys and lambda_q16, evals, g0
+        (signed), xw0 and line_ms.  Afterwards flow_fetch() returns the flow,
+        loads_fetch() the last loading and get_weights() the final weights."""
+        self.prepare(s, t)
+        return self.assign_line_run(capacity, iters, demand, a, power, **search_opts)
+
+    def assign_line_run(self, capacity, iters: int, demand=None, a=(3, 20), power: int = 4,
+                        prefix_bytes=0, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
+                        capacity_cols=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,
+                        capacity_max=0):
+        """cpd_query_assign_line on the prepared queries (capacity_cols as in
+        assign_run)."""
+        self._path_offsets = None
+        c = self._capacity(capacity)
+        d = None
+        if demand is not None:
+            d = _u32(demand)
+            if d.shape != (self._nq,):
+                raise ValueError("demand must have one entry per prepared query")
+        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
+                       int(capacity_cols), int(virtual_tick_ns), SEARCH_FORMS[tables],
+                       float(workspace_frac), int(capacity_max))
+        f = Vdf(int(a[0]), int(a[1]), int(power), 1)
+        n = max(0, min(int(iters), 65535))
+        out = (AssignLineIter * max(1, n))()
+        done = C.c_uint32()
+        rc = lib.cpd_query_assign_line(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)),
+                                       _ptr(d, u32p), _ptr(c, u32p), C.byref(f),
+                                       C.c_uint32(int(iters) & 0xFFFFFFFF), out, C.byref(done))
+        if rc == CPD_OK or (rc in (CPD_E_OOM, CPD_E_RANGE)
+                            and "iteration" in lib.cpd_last_error().decode()):
+            self._load_slices = 1  # a loading is resident
+        _check(rc)
+        recs = []
+        for r in out[:done.value]:
+            recs.append({"finished": r.finished, "sptt": (r.sptt_hi << 64) | r.sptt_lo,
+                         "tstt": (r.tstt_hi << 64) | r.tstt_lo, "moves": r.moves,
+                         "changed": r.changed, "search_ms": r.search_ms,
+                         "loads_ms": r.loads_ms, "vdf_ms": r.vdf_ms,
+                         "lambda_q16": r.lambda_q16, "evals": r.evals,
+                         "g0": _s128(r.g0_lo, r.g0_hi), "xw0": (r.xw0_hi << 64) | r.xw0_lo,
+                         "line_ms": r.line_ms})
         return recs
 
     def __del__(self):

@@ -147,6 +147,157 @@ __global__ __launch_bounds__(256) void sptt_reduce(const unsigned long long* __r
     wave_sum128(sum, finished, acc);
 }
 
+// --- the flow step (cpd_api.h "The flow step") -----------------------------
+
+// a += sign(d) * |d| * w in two's complement: what wave_sum128 adds mod 2^128
+__device__ __forceinline__ void mad128_signed(U128& a, long long d, unsigned long long w) {
+    const unsigned long long mag = d < 0 ? 0ull - (unsigned long long)d : (unsigned long long)d;
+    unsigned long long lo = mag * w, hi = __umul64hi(mag, w);
+    if (d < 0) {  // minus (hi, lo)
+        lo = 0ull - lo;
+        hi = ~hi + (lo == 0ull ? 1ull : 0ull);
+    }
+    add128(a, lo, hi);
+}
+
+// X + floor(lam * d / 2^16), lam <= 65536: the product (up to 80 bits) is kept
+// in two halves; for d < 0 the floor is minus the ceiling of the magnitude.
+__device__ __forceinline__ unsigned long long flow_at(unsigned long long X, long long d,
+                                                      unsigned long long lam) {
+    const unsigned long long mag = d < 0 ? 0ull - (unsigned long long)d : (unsigned long long)d;
+    unsigned long long lo = mag * lam, hi = __umul64hi(mag, lam);
+    if (d < 0) {
+        lo += 65535ull;
+        hi += lo < 65535ull ? 1ull : 0ull;
+    }
+    const unsigned long long q = (lo >> 16) | (hi << 48);  // <= |d| < 2^63
+    return d < 0 ? X - q : X + q;
+}
+
+// g(lambda) of the record in st (see FlowState in assign_kernels.hpp): a lane
+// per slot, grid-stride.  Slots with D == 0 add nothing to g and skip the
+// delay function.  first != 0 (the lambda = 0 pass): also the sum of X * w(0)
+// into st[kFlowXw] and the largest counter of Y into st[kFlowMaxY].
+__global__ __launch_bounds__(256) void flow_line_eval(const unsigned long long* __restrict__ Y,
+                                                      const unsigned long long* __restrict__ X,
+                                                      const uint2* __restrict__ adj_free,
+                                                      const uint32_t* __restrict__ cap_slot,
+                                                      unsigned long long nslots, cpd_vdf f,
+                                                      uint32_t first,
+                                                      unsigned long long* __restrict__ st) {
+    if (st[kFlowDone] != 0ull) return;
+    const unsigned long long lam = st[kFlowLambda];
+    U128 g{0ull, 0ull}, xw{0ull, 0ull};
+    unsigned long long ymax = 0;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < nslots; i += step) {
+        const unsigned long long y = Y[i], x = X[i];
+        if (first && y > ymax) ymax = y;
+        // wraps for a counter the range check refuses: the sums are then unused
+        const long long d = (long long)((y << 16) - x);
+        if (d == 0 && !(first && x)) continue;
+        const uint2 a = adj_free[i];
+        if (a.x == 0xFFFFFFFFu) continue;  // padding: Y and X are 0 there anyway
+        const unsigned long long xl = flow_at(x, d, lam);
+        const uint32_t w = vdf_weight(a.y, xl >> 16, cap_slot[i], f);
+        mad128_signed(g, d, w);
+        if (first) mad128(xw, x, w);
+    }
+    wave_sum128(g, 0ull, st + kFlowG);
+    if (first) {
+        wave_sum128(xw, 0ull, st + kFlowXw);
+        for (int d = 32; d > 0; d >>= 1) {
+            const unsigned long long o = __shfl_down(ymax, d, 64);
+            ymax = o > ymax ? o : ymax;
+        }
+        if ((threadIdx.x & 63u) == 0u && ymax) atomicMax(&st[kFlowMaxY], ymax);
+    }
+}
+
+// One lane: reads g(lambda) from the accumulator, advances the record by one
+// step of the line rule (or takes the caller's lambda when want <= 65536) and
+// zeroes the accumulator for the next evaluation.  Plain stores from lane 0.
+__global__ __launch_bounds__(64) void flow_line_decide(uint32_t want,
+                                                       unsigned long long* __restrict__ st) {
+    if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+    if (st[kFlowDone] != 0ull) return;
+    const bool neg = (long long)st[kFlowG + 1] < 0;  // g < 0
+    const unsigned long long phase = st[kFlowPhase];
+    st[kFlowEvals] += 1ull;
+    if (phase == 0ull) {  // g(0)
+        st[kFlowG0] = st[kFlowG];
+        st[kFlowG0 + 1] = st[kFlowG + 1];
+        if (st[kFlowMaxY] >= (1ull << 47)) {
+            st[kFlowDone] = 2ull;  // refused: nothing is applied
+        } else if (want <= 65536u) {
+            st[kFlowLambda] = want;
+            st[kFlowDone] = 1ull;
+        } else if (!neg) {
+            st[kFlowLambda] = 0ull;
+            st[kFlowDone] = 1ull;
+        } else {
+            st[kFlowLambda] = 65536ull;
+            st[kFlowPhase] = 1ull;
+        }
+    } else if (phase == 1ull) {  // g(65536)
+        if (neg) {
+            st[kFlowDone] = 1ull;
+        } else {
+            st[kFlowLo] = 0ull;
+            st[kFlowHi] = 65536ull;
+            st[kFlowLambda] = 32768ull;
+            st[kFlowPhase] = 2ull;
+        }
+    } else {  // g(mid)
+        unsigned long long lo = st[kFlowLo], hi = st[kFlowHi];
+        if (neg) lo = st[kFlowLambda];
+        else hi = st[kFlowLambda];
+        st[kFlowLo] = lo;
+        st[kFlowHi] = hi;
+        if (hi - lo > 1ull) {
+            st[kFlowLambda] = (lo + hi) >> 1;
+        } else {
+            st[kFlowLambda] = hi;
+            st[kFlowDone] = 1ull;
+        }
+    }
+    st[kFlowG] = st[kFlowG + 1] = st[kFlowG + 2] = 0ull;
+}
+
+// X <- X(lambda) and the selected adjacency <- (dst, w(lambda)) with the
+// record's lambda; padding slots are copied from adj_free, their X left alone.
+// The sum of (X >> 16) * w' and the changed count as vdf_update<0> forms them.
+__global__ __launch_bounds__(256) void flow_apply(const unsigned long long* __restrict__ Y,
+                                                  unsigned long long* __restrict__ X,
+                                                  const uint2* __restrict__ adj_free,
+                                                  const uint32_t* __restrict__ cap_slot,
+                                                  unsigned long long nslots, cpd_vdf f,
+                                                  uint2* __restrict__ adj_out,
+                                                  unsigned long long* __restrict__ st) {
+    if (st[kFlowDone] != 1ull) return;
+    const unsigned long long lam = st[kFlowLambda];
+    U128 sum{0ull, 0ull};
+    unsigned long long changed = 0;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < nslots; i += step) {
+        uint2 a = adj_free[i];
+        if (a.x != 0xFFFFFFFFu) {
+            const unsigned long long x = X[i];
+            const long long d = (long long)((Y[i] << 16) - x);
+            const unsigned long long xn = d ? flow_at(x, d, lam) : x;
+            if (xn != x) X[i] = xn;
+            const uint32_t w = vdf_weight(a.y, xn >> 16, cap_slot[i], f);
+            mad128(sum, xn >> 16, w);
+            changed += w != a.y ? 1ull : 0ull;
+            a.y = w;
+        }
+        adj_out[i] = a;
+    }
+    wave_sum128(sum, changed, st + kFlowTstt);
+}
+
 }  // namespace kern
 
 namespace {
@@ -199,6 +350,30 @@ void launch_sptt_reduce(const uint64_t* cost, const uint8_t* fin, const uint32_t
     hipLaunchKernelGGL(kern::sptt_reduce, dim3(stride_grid(nq)), dim3(256), 0, s,
                        reinterpret_cast<const unsigned long long*>(cost), fin, qperm, demand, nq,
                        acc);
+}
+
+void launch_flow_line_eval(const uint64_t* Y, const uint64_t* X, const uint32_t* adj_free,
+                           const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f, bool first,
+                           unsigned long long* st, hipStream_t s) {
+    hipLaunchKernelGGL(kern::flow_line_eval, dim3(stride_grid(nslots)), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long*>(Y),
+                       reinterpret_cast<const unsigned long long*>(X),
+                       reinterpret_cast<const uint2*>(adj_free), cap_slot, nslots, f,
+                       first ? 1u : 0u, st);
+}
+
+void launch_flow_line_decide(uint32_t want, unsigned long long* st, hipStream_t s) {
+    hipLaunchKernelGGL(kern::flow_line_decide, dim3(1), dim3(64), 0, s, want, st);
+}
+
+void launch_flow_apply(const uint64_t* Y, uint64_t* X, const uint32_t* adj_free,
+                       const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f, uint32_t* adj_out,
+                       unsigned long long* st, hipStream_t s) {
+    hipLaunchKernelGGL(kern::flow_apply, dim3(stride_grid(nslots)), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long*>(Y),
+                       reinterpret_cast<unsigned long long*>(X),
+                       reinterpret_cast<const uint2*>(adj_free), cap_slot, nslots, f,
+                       reinterpret_cast<uint2*>(adj_out), st);
 }
 
 }  // namespace cpd

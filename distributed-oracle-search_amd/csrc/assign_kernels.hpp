@@ -48,4 +48,42 @@ void launch_sptt_reduce(const uint64_t* cost, const uint8_t* fin, const uint32_t
                         const uint32_t* demand, uint32_t nq, unsigned long long* acc,
                         hipStream_t s);
 
+// The flow step (cpd_api.h "The flow step").  Its state is one array of
+// kFlowWords u64 in device memory, zeroed by the caller before a step; the
+// kernels below communicate through it alone, so a whole line search is queued
+// without a host synchronise and read back once:
+enum : uint32_t {
+    kFlowG = 0,       // +0, +1: g(lambda) being summed (signed 128), +2 unused
+    kFlowXw = 3,      // +0, +1: the sum of X * w(0) (unsigned 128), +2 unused
+    kFlowMaxY = 6,    // the largest counter of Y
+    kFlowTstt = 7,    // +0, +1: the sum of (X' >> 16) * w', +2: edges with w' != w0
+    kFlowLo = 10,     // the bisection's bracket
+    kFlowHi = 11,
+    kFlowLambda = 12, // the lambda the next evaluation takes; the step once done
+    kFlowDone = 13,   // 0: searching, 1: lambda is final, 2: refused (a counter >= 2^47)
+    kFlowEvals = 14,  // evaluations of g made
+    kFlowG0 = 15,     // +0, +1: g(0)
+    kFlowPhase = 17,  // 0: g(0) is next, 1: g(65536), 2: g(mid)
+    kFlowWords = 18
+};
+// launch_flow_line_eval: st[kFlowG ..] += the sum over the real slots of D *
+// w(lambda), D = (Y << 16) - X, lambda = st[kFlowLambda]; `first` (the lambda
+// = 0 pass) also sums X * w(0) and takes the maximum of Y.  Returns at once
+// when st[kFlowDone] is set.  Y, X: nslots u64 in slot order; adj_free and
+// cap_slot as launch_vdf_update reads them.
+// launch_flow_line_decide: one lane advances the record by the evaluation just
+// made — the line rule of cpd_api.h for want > 65536, else lambda = want after
+// g(0) — and zeroes st[kFlowG ..].  18 eval / decide pairs end every line
+// search (g(0), g(65536), 16 halvings of 0..65536).
+// launch_flow_apply: with st[kFlowDone] == 1, X <- X(lambda), adj_out <- (dst,
+// w(lambda)) per real slot (padding slots copied from adj_free), st[kFlowTstt
+// ..] += the sums; does nothing otherwise.
+void launch_flow_line_eval(const uint64_t* Y, const uint64_t* X, const uint32_t* adj_free,
+                           const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f, bool first,
+                           unsigned long long* st, hipStream_t s);
+void launch_flow_line_decide(uint32_t want, unsigned long long* st, hipStream_t s);
+void launch_flow_apply(const uint64_t* Y, uint64_t* X, const uint32_t* adj_free,
+                       const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f, uint32_t* adj_out,
+                       unsigned long long* st, hipStream_t s);
+
 }  // namespace cpd

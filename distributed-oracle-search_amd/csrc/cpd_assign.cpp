@@ -119,6 +119,108 @@ void fetch_weights(cpd_index* ix, const uint32_t* src, uint32_t stride, uint32_t
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// What the flow step asks of the resident load table.
+void check_flow_table(const cpd_index* ix, const char* who) {
+    const std::string w(who);
+    CPD_REQUIRE(ix->loads_ready, CPD_E_ARG,
+                w + ": no load table resident (cpd_query_loads with nslices = 1 or "
+                    "cpd_query_search_loads first)");
+    CPD_REQUIRE(ix->ld_period == 0, CPD_E_ARG,
+                w + ": the resident load table is a timed walk's (period " +
+                    std::to_string(ix->ld_period) + "), the flow step needs one plane");
+    CPD_REQUIRE(ix->ld_slices == 1u, CPD_E_ARG,
+                w + ": the resident load table has " + std::to_string(ix->ld_slices) +
+                    " slices, the flow step needs one plane");
+}
+
+// The flow step over the resident one-plane table with the slot-order
+// capacities in place: every evaluate / decide pair of the line search and the
+// apply pass are queued at once; the host reads the state once, afterwards.
+void flow_step(cpd_index* ix, const cpd_vdf& f, uint32_t lambda_q16, cpd_flow_info* info) {
+    cpd_graph* g = ix->g;
+    hipStream_t s = g->stream;
+    const uint64_t nslots = (uint64_t)g->n << g->adj_shift;
+    const bool init = !ix->flow_ready;  // no flow table: X = Y << 16 whatever lambda says
+    {
+        ArenaScope carve;
+        ix->fl_tab.alloc((size_t)nslots);
+        ix->fl_st.alloc(kFlowWords);
+        ix->adj_sel.alloc((size_t)(2u * nslots));
+    }
+    if (init) HIP_CHECK(hipMemsetAsync(ix->fl_tab.p, 0, (size_t)nslots * sizeof(uint64_t), s));
+    HIP_CHECK(hipMemsetAsync(ix->fl_st.p, 0, kFlowWords * sizeof(unsigned long long), s));
+    const uint32_t want = init ? 65536u : lambda_q16;
+    const uint32_t pairs = want <= 65536u ? 1u : 18u;
+    Events<3> ev(g);
+    HIP_CHECK(hipEventRecord(ev.e[0], s));
+    (void)hipGetLastError();
+    for (uint32_t i = 0; i < pairs; ++i) {
+        launch_flow_line_eval(ix->ld_tab.p, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f,
+                              i == 0u, ix->fl_st.p, s);
+        launch_flow_line_decide(want, ix->fl_st.p, s);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[1], s));
+    launch_flow_apply(ix->ld_tab.p, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f,
+                      ix->adj_sel.p, ix->fl_st.p, s);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[2], s));
+    unsigned long long h[kFlowWords] = {};
+    HIP_CHECK(hipMemcpyAsync(h, ix->fl_st.p, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (h[kFlowDone] != 1ull) {
+        // refused by the decide kernel, nothing was applied: name the first edge
+        std::vector<uint64_t> loads(g->m);
+        ix->ld_out.alloc(g->m);
+        (void)hipGetLastError();
+        launch_loads_gather(ix->ld_tab.p, g->slot_of_edge_d.p, g->m, (uint32_t)nslots, 1u,
+                            ix->ld_out.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(loads.data(), ix->ld_out.p, (size_t)g->m * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        uint32_t e = 0;
+        while (e < g->m && loads[e] < (1ull << 47)) ++e;
+        throw Error(CPD_E_RANGE, "flow step: load " + std::to_string(e < g->m ? loads[e] : 0ull) +
+                                     " on edge " + std::to_string(e) +
+                                     " (every counter must be below 2^47)");
+    }
+    ix->flow_ready = true;
+    ix->custom_w = true;
+    ix->c_ready = false;  // the search's incumbent tables follow the weights
+    float line_ms = 0.f, apply_ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&line_ms, ev.e[0], ev.e[1]));
+    HIP_CHECK(hipEventElapsedTime(&apply_ms, ev.e[1], ev.e[2]));
+    if (g->timing) {
+        // per evaluation and slot: Y, X, the free-flow pair, the capacity (28
+        // B); the apply also writes X and the selected pair
+        Agg& ae = g->agg["flow_line_eval"];
+        ae.launches += h[kFlowEvals];
+        ae.ms += line_ms;
+        ae.bytes += (double)nslots * 28.0 * (double)h[kFlowEvals];
+        Agg& aa = g->agg["flow_apply"];
+        aa.launches++;
+        aa.ms += apply_ms;
+        aa.bytes += (double)nslots * 44.0;
+    }
+    if (info) {
+        *info = cpd_flow_info{};
+        info->lambda_q16 = (uint32_t)h[kFlowLambda];
+        if (!init) {  // the initialising step reports no evaluation
+            info->evals = (uint32_t)h[kFlowEvals];
+            info->g0_lo = h[kFlowG0];
+            info->g0_hi = h[kFlowG0 + 1];
+            info->xw0_lo = h[kFlowXw];
+            info->xw0_hi = h[kFlowXw + 1];
+        }
+        info->tstt_lo = h[kFlowTstt];
+        info->tstt_hi = h[kFlowTstt + 1];
+        info->changed = h[kFlowTstt + 2];
+        info->line_ms = line_ms;
+        info->apply_ms = apply_ms;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,6 +332,141 @@ int cpd_query_assign(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix
             r.search_ms = ss.kernel_ms + ss.tables_ms;
             r.loads_ms = li.loads_ms;
             r.vdf_ms = vi.vdf_ms + (k == 1 ? cap_ms : 0.f);
+        }
+    });
+}
+
+int cpd_index_flow_step(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f,
+                        uint32_t lambda_q16, cpd_flow_info* info) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "flow step: null index");
+        check_vdf(f, false, "flow step");
+        CPD_REQUIRE(lambda_q16 <= 65536u || lambda_q16 == CPD_STEP_LINE, CPD_E_ARG,
+                    "flow step: lambda_q16 " + std::to_string(lambda_q16) +
+                        " is neither 0..65536 nor CPD_STEP_LINE");
+        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
+                    "flow step: index incomplete (" + std::to_string(ix->added) + " of " +
+                        std::to_string(ix->nrows) + " rows appended)");
+        check_flow_table(ix, "flow step");
+        check_capacity(ix, capacity, "flow step");
+        ix->g->select();
+        upload_capacity(ix, capacity);
+        flow_step(ix, *f, lambda_q16, info);
+    });
+}
+
+int cpd_index_flow_fetch(cpd_index* ix, uint64_t* flow) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "flow fetch: null index");
+        CPD_REQUIRE(ix->flow_ready, CPD_E_ARG,
+                    "flow fetch: no flow table resident (cpd_index_flow_step first)");
+        cpd_graph* g = ix->g;
+        if (!g->m) return;
+        CPD_REQUIRE(flow, CPD_E_ARG, "flow fetch: null argument");
+        g->select();
+        hipStream_t s = g->stream;
+        ix->fl_out.alloc(g->m);
+        (void)hipGetLastError();
+        launch_loads_gather(ix->fl_tab.p, g->slot_of_edge_d.p, g->m, g->n << g->adj_shift, 1u,
+                            ix->fl_out.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(flow, ix->fl_out.p, (size_t)g->m * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int cpd_index_flow_clear(cpd_index* ix) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "flow clear: null index");
+        ix->g->select();
+        ix->fl_tab.release();
+        ix->fl_out.release();
+        ix->flow_ready = false;
+    });
+}
+
+int cpd_query_assign_line(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                          const uint32_t* demand, const uint32_t* capacity, const cpd_vdf* f,
+                          uint32_t iters, cpd_assign_line_iter* out, uint32_t* done) {
+    return guarded([&] {
+        CPD_REQUIRE(ix && out && done, CPD_E_ARG, "assign line: null argument");
+        CPD_REQUIRE(iters >= 1u && iters <= 65535u, CPD_E_ARG,
+                    "assign line: " + std::to_string(iters) + " iterations, 1 to 65535");
+        check_vdf(f, false, "assign line");
+        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
+                    "assign line: index incomplete (" + std::to_string(ix->added) + " of " +
+                        std::to_string(ix->nrows) + " rows appended)");
+        check_capacity(ix, capacity, "assign line");
+        for (uint32_t k = 0; k < iters; ++k) out[k] = cpd_assign_line_iter{};
+        *done = 0;
+        cpd_graph* g = ix->g;
+        g->select();
+        hipStream_t s = g->stream;
+        const uint32_t nq = ix->nq;
+        float cap_ms = 0.f;
+        for (uint32_t k = 1; k <= iters; ++k) {
+            cpd_assign_line_iter& r = out[k - 1];
+            cpd_search_stats ss{};
+            cpd_search_loads_info li{};
+            const int rc = cpd_query_search_loads(ix, opts, prefix_bytes, demand, 0u, &ss, &li);
+            if (rc != CPD_OK) {
+                const std::string why = cpd_last_error();
+                if (k == 1) throw Error(rc, why);  // nothing has changed
+                throw Error(rc, "assign line: iteration " + std::to_string(k) + " of " +
+                                    std::to_string(iters) + " failed, the flow table and weights "
+                                    "are those of " + std::to_string(k - 1) + " iterations: " + why);
+            }
+            if (k == 1) {
+                // the loop starts from an empty flow table; the capacities are
+                // uploaded once, after the first loading succeeded
+                ix->flow_ready = false;
+                Events<2> ev(g);
+                HIP_CHECK(hipEventRecord(ev.e[0], s));
+                upload_capacity(ix, capacity);
+                HIP_CHECK(hipEventRecord(ev.e[1], s));
+                HIP_CHECK(hipStreamSynchronize(s));
+                HIP_CHECK(hipEventElapsedTime(&cap_ms, ev.e[0], ev.e[1]));
+            }
+            HIP_CHECK(hipMemsetAsync(ix->vdf_acc.p, 0, 3 * sizeof(unsigned long long), s));
+            (void)hipGetLastError();
+            launch_sptt_reduce(ix->cost.p, ix->fin.p, ix->qperm.p,
+                               demand && nq ? ix->ld_demand.p : nullptr, nq, ix->vdf_acc.p, s);
+            HIP_CHECK(hipGetLastError());
+            unsigned long long h[3] = {0, 0, 0};
+            HIP_CHECK(hipMemcpyAsync(h, ix->vdf_acc.p, sizeof h, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            cpd_flow_info fi{};
+            try {
+                flow_step(ix, *f, CPD_STEP_LINE, &fi);
+            } catch (const Error& e) {
+                if (k == 1) throw;
+                throw Error(e.code, "assign line: iteration " + std::to_string(k) + " of " +
+                                        std::to_string(iters) + " failed, the flow table and "
+                                        "weights are those of " + std::to_string(k - 1) +
+                                        " iterations: " + e.what());
+            }
+            r.finished = h[2];
+            r.sptt_lo = h[0];
+            r.sptt_hi = h[1];
+            r.tstt_lo = fi.tstt_lo;
+            r.tstt_hi = fi.tstt_hi;
+            r.moves = li.moves;
+            r.changed = fi.changed;
+            r.search_ms = ss.kernel_ms + ss.tables_ms;
+            r.loads_ms = li.loads_ms;
+            r.vdf_ms = fi.apply_ms + (k == 1 ? cap_ms : 0.f);
+            r.lambda_q16 = fi.lambda_q16;
+            r.evals = fi.evals;
+            r.g0_lo = fi.g0_lo;
+            r.g0_hi = fi.g0_hi;
+            r.xw0_lo = fi.xw0_lo;
+            r.xw0_hi = fi.xw0_hi;
+            r.line_ms = fi.line_ms;
+            *done = k;
+            // lambda = 0: the weights stay, the next search would repeat this
+            // one; the empty batch has nothing to iterate
+            if ((k >= 2u && fi.lambda_q16 == 0u) || nq == 0u) break;
         }
     });
 }

@@ -539,6 +539,14 @@ struct cpd_index {
     // fetch (cpd_index_get_weights / _weight_sets).  Carved like ld_tab.
     DevBuf<uint32_t> vdf_cap_in, vdf_cap, vdf_out;
     DevBuf<unsigned long long> vdf_acc;
+    // the flow step (cpd_index_flow_step, cpd_query_assign_line): the flow
+    // table — one u64 X (Q16) per adjacency slot, the load table's order —
+    // kept until cpd_index_flow_clear, independent of ld_tab; the step's
+    // device state (kFlowWords, assign_kernels.hpp) and the fetch's
+    // edge-order copy.  Carved like ld_tab.
+    DevBuf<uint64_t> fl_tab, fl_out;
+    DevBuf<unsigned long long> fl_st;
+    bool flow_ready = false;
 };
 
 template <class F>

@@ -14,8 +14,8 @@
 //                                           only: also write every edge's load)
 //             [--timed P [--loads]]  (table-search only: cost, and load, every
 //                                     move under the diff of its clock time)
-//             [--assign K --capacity C [--vdf A/B^P]]  (cpd-search only: K
-//                                     iterations of load and re-weight)
+//             [--assign K --capacity C [--vdf A/B^P] [--step msa|line]]  (cpd-search
+//                                     only: K iterations of load and re-weight)
 //             [--verbose]  (per request on stderr: read+parse / prepare / compute)
 //
 // Creates its request FIFO, streams the CPD buckets this worker owns onto its
@@ -102,6 +102,14 @@
 // and renamed into place).  A .diff names an edge by its endpoints, so of
 // parallel edges only the first can be re-weighted by it.  Every request
 // starts again from its diff: nothing is carried from one request to the next.
+// --step line (with --assign; --step msa is the default and changes nothing)
+// answers through cpd_query_assign_line instead: the line-search step over the
+// flow table (cpd_api.h "The flow step"), at most K iterations — the loop ends
+// early after an iteration k >= 2 whose step is 0.  <query file>.assign then
+// holds one line per iteration made, "k finished sptt tstt moves changed lambda
+// g0 xw0" (lambda in Q16, 0..65536; g0 signed; -g0 / xw0 is the relative gap
+// before step k), <query file>.loads the volumes X >> 16 of the final flow in
+// the same one-column format, and <query file>.diff the final weights as before.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -242,12 +250,9 @@ static void write_costs(cpd_index* ix, const std::string& qfile, const std::vect
     }
 }
 
-// <query file>.loads of a --loads request: edge from to load_0 ... per loaded edge
-static void write_loads(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g,
-                        size_t slices) {
-    std::vector<uint64_t> loads(slices * g.m);
-    if (cpd_query_loads_fetch(ix, loads.data()) != CPD_OK)
-        throw std::runtime_error(cpd_last_error());
+// <query file>.loads: edge from to load_0 ... per edge with any non-zero value
+static void write_load_values(const std::string& qfile, const cpd::io::XYGraph& g, size_t slices,
+                              const std::vector<uint64_t>& loads) {
     const std::string path = qfile + ".loads", tmp = path + ".tmp";
     std::FILE* f = std::fopen(tmp.c_str(), "w");
     if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
@@ -269,6 +274,23 @@ static void write_loads(cpd_index* ix, const std::string& qfile, const cpd::io::
     }
 }
 
+// <query file>.loads of a --loads request: the resident table
+static void write_loads(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g,
+                        size_t slices) {
+    std::vector<uint64_t> loads(slices * g.m);
+    if (cpd_query_loads_fetch(ix, loads.data()) != CPD_OK)
+        throw std::runtime_error(cpd_last_error());
+    write_load_values(qfile, g, slices, loads);
+}
+
+// <query file>.loads of an --assign --step line request: the flow's volumes
+static void write_flow(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g) {
+    std::vector<uint64_t> x(g.m);
+    if (cpd_index_flow_fetch(ix, x.data()) != CPD_OK) throw std::runtime_error(cpd_last_error());
+    for (uint64_t& v : x) v >>= 16;
+    write_load_values(qfile, g, 1, x);
+}
+
 // a 128-bit unsigned value in decimal
 static std::string dec128(uint64_t lo, uint64_t hi) {
     unsigned __int128 v = ((unsigned __int128)hi << 64) | lo;
@@ -277,18 +299,23 @@ static std::string dec128(uint64_t lo, uint64_t hi) {
     return d;
 }
 
-// <query file>.assign and <query file>.diff of an --assign request
+// a 128-bit signed value (two's complement halves) in decimal
+static std::string dec128_signed(uint64_t lo, uint64_t hi) {
+    if (!(hi >> 63)) return dec128(lo, hi);
+    const unsigned __int128 v = ~(((unsigned __int128)hi << 64) | lo) + 1u;
+    return "-" + dec128((uint64_t)v, (uint64_t)(v >> 64));
+}
+
+// <query file>.assign and <query file>.diff of an --assign request: one line
+// of text per iteration, then the final weights
 static void write_assign(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g,
-                         const std::vector<cpd_assign_iter>& it) {
+                         const std::vector<std::string>& lines) {
     std::string path = qfile + ".assign", tmp = path + ".tmp";
     std::FILE* f = std::fopen(tmp.c_str(), "w");
     if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
     bool ok = true;
-    for (size_t k = 0; k < it.size() && ok; ++k)
-        ok = std::fprintf(f, "%zu %llu %s %s %llu %llu\n", k + 1, (unsigned long long)it[k].finished,
-                          dec128(it[k].sptt_lo, it[k].sptt_hi).c_str(),
-                          dec128(it[k].tstt_lo, it[k].tstt_hi).c_str(),
-                          (unsigned long long)it[k].moves, (unsigned long long)it[k].changed) > 0;
+    for (size_t k = 0; k < lines.size() && ok; ++k)
+        ok = std::fprintf(f, "%zu %s\n", k + 1, lines[k].c_str()) > 0;
     ok = std::fclose(f) == 0 && ok;
     if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
         ::unlink(tmp.c_str());
@@ -452,7 +479,12 @@ int main(int argc, char** argv) {
                      "                  delay w0 (1 + A/B (x/C)^P), default 3/20^4); writes <query "
                      "file>.loads,\n"
                      "                  .assign (k finished sptt tstt moves changed) and .diff (the "
-                     "final weights)\n");
+                     "final weights)\n"
+                     "       [--step msa|line]  with --assign: msa (default) as above; line answers "
+                     "through\n"
+                     "                  cpd_query_assign_line (the line-search step): .assign lines "
+                     "end in\n"
+                     "                  lambda g0 xw0, .loads holds the final flow's volumes\n");
         return 2;
     }
     // table-search (make_fifos.py:20) or the CPD-heuristic search
@@ -551,6 +583,12 @@ int main(int argc, char** argv) {
         }
         vdf = cpd_vdf{an, ad, pw, 1};
     }
+    const std::string step = a.str("step", "msa");
+    if ((a.has("step") && !assign) || (step != "msa" && step != "line")) {
+        std::fprintf(stderr, "fifo_auto: --step msa|line needs --assign\n");
+        return 2;
+    }
+    const bool step_line = step == "line";
     int mcode = cli::method_code(method);
     std::string xy = inputs[0];
     std::string outdir = a.str("outdir", ".");
@@ -867,12 +905,44 @@ int main(int argc, char** argv) {
                 active_diff.clear();
                 static std::vector<uint32_t> cap;
                 cap.assign(g.m, (uint32_t)assign_cap);
-                std::vector<cpd_assign_iter> it((size_t)assign_iters);
-                rc = cpd_query_assign(ix, &so, 0, nullptr, cap.data(), &vdf, (uint32_t)assign_iters,
-                                      it.data());
-                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                write_loads(ix, qfile, g, 1);
-                write_assign(ix, qfile, g, it);
+                // one record per iteration: what both loops report, then the
+                // line rule's step and gap terms
+                auto common = [](uint64_t finished, uint64_t sl, uint64_t sh, uint64_t tl, uint64_t th,
+                                 uint64_t moves, uint64_t changed) {
+                    return std::to_string(finished) + " " + dec128(sl, sh) + " " + dec128(tl, th) +
+                           " " + std::to_string(moves) + " " + std::to_string(changed);
+                };
+                std::vector<std::string> lines;
+                double search_ms = 0.0;
+                if (step_line) {
+                    std::vector<cpd_assign_line_iter> it((size_t)assign_iters);
+                    uint32_t made = 0;
+                    rc = cpd_query_assign_line(ix, &so, 0, nullptr, cap.data(), &vdf,
+                                               (uint32_t)assign_iters, it.data(), &made);
+                    if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                    for (uint32_t k = 0; k < made; ++k) {
+                        const cpd_assign_line_iter& r = it[k];
+                        lines.push_back(common(r.finished, r.sptt_lo, r.sptt_hi, r.tstt_lo, r.tstt_hi,
+                                               r.moves, r.changed) +
+                                        " " + std::to_string(r.lambda_q16) + " " +
+                                        dec128_signed(r.g0_lo, r.g0_hi) + " " +
+                                        dec128(r.xw0_lo, r.xw0_hi));
+                        search_ms += r.search_ms;
+                    }
+                    write_flow(ix, qfile, g);
+                } else {
+                    std::vector<cpd_assign_iter> it((size_t)assign_iters);
+                    rc = cpd_query_assign(ix, &so, 0, nullptr, cap.data(), &vdf,
+                                          (uint32_t)assign_iters, it.data());
+                    if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                    for (const cpd_assign_iter& r : it) {
+                        lines.push_back(common(r.finished, r.sptt_lo, r.sptt_hi, r.tstt_lo, r.tstt_hi,
+                                               r.moves, r.changed));
+                        search_ms += r.search_ms;
+                    }
+                    write_loads(ix, qfile, g, 1);
+                }
+                write_assign(ix, qfile, g, lines);
                 // the answer line's sums, from the last iteration's search
                 std::vector<uint32_t> cnt(5 * nq), plen(nq);
                 std::vector<uint8_t> fin(nq);
@@ -888,8 +958,8 @@ int main(int argc, char** argv) {
                         ss.overflow++;
                     }
                 }
-                ss.kernel_ms = ss.tables_ms = 0.0;
-                for (const auto& r : it) ss.kernel_ms += r.search_ms;  // tables included
+                ss.tables_ms = 0.0;
+                ss.kernel_ms = search_ms;  // tables included
                 if (ss.overflow)
                     std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
                                  (unsigned long long)ss.overflow);

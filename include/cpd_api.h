@@ -851,7 +851,8 @@ int  cpd_index_get_weight_sets(cpd_index* ix, uint32_t* nsets, uint32_t* w /* ns
  * Out of scope: a demand set larger than one prepared batch (write the loop
  * from cpd_query_search_loads(CPD_LOADS_ACCUMULATE) and
  * cpd_index_weights_from_loads(load_div), which is why both are public); a
- * time-dependent search; line search, Frank-Wolfe and other step rules.     */
+ * time-dependent search; conjugate and bi-conjugate Frank-Wolfe (the line
+ * search step is cpd_query_assign_line below).                              */
 typedef struct cpd_assign_iter {
     uint64_t finished;          /* queries with finished == 1 in this iteration  */
     uint64_t sptt_lo, sptt_hi;  /* sum over those of demand[q] * cost[q], under the weights searched with */
@@ -864,6 +865,113 @@ int  cpd_query_assign(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefi
                       const uint32_t* capacity /* m, edge order, >= 1 */,
                       const cpd_vdf* f /* load_div ignored */, uint32_t iters /* 1..65535 */,
                       cpd_assign_iter* out /* iters records */);
+
+/* The flow step — a line search (the Frank-Wolfe step rule) in place of
+ * MSA's 1/k.  A FLOW TABLE is state of the index of its own: one u64 X per
+ * adjacency slot, in the load table's slot order, the volume in Q16 (x = X >>
+ * 16).  It is independent of the load table (cpd_query_loads_clear leaves it
+ * alone), lives until cpd_index_flow_clear or cpd_index_free, and is carved
+ * from the arena as the load table is.  Let Y be the resident ONE-PLANE load
+ * table (cpd_query_loads with nslices = 1, cpd_query_search_loads): the
+ * all-or-nothing loading to step towards.  For a slot holding a real edge with
+ * free-flow weight w0 and capacity c:
+ *     D      = (Y << 16) - X                     signed
+ *     X(l)   = X + floor(l * D / 2^16)           l = lambda in 0..65536; the
+ *                                                product is formed exactly (it
+ *                                                can need 80 bits), the floor
+ *                                                is toward minus infinity
+ *     w(l)   = the delay function above at x = X(l) >> 16, load_div = 1
+ *     g(l)   = sum over the slots of D * w(l)    signed 128 bits, exact
+ * X(0) = X, X(65536) = Y << 16, and X(l) stays between them.  Every counter of
+ * Y must be below 2^47 (so that Y << 16 < 2^63): CPD_E_RANGE otherwise, naming
+ * the first offending edge, with nothing changed.  |D * w| < 2^95 over fewer
+ * than 2^32 slots, so g fits; integer adds commute, so every value is exact
+ * and the same in every run.
+ * The line rule (lambda_q16 == CPD_STEP_LINE), a procedure, so that truncation
+ * in g cannot make two implementations disagree:
+ *   1. g(0) >= 0: lambda = 0;
+ *   2. else g(65536) < 0: lambda = 65536;
+ *   3. else lo = 0, hi = 65536; while hi - lo > 1: mid = (lo + hi) >> 1; g(mid)
+ *      < 0 ? lo = mid : hi = mid; then lambda = hi.
+ * At most 18 evaluations of g.  An explicit lambda_q16 in 0..65536 skips the
+ * rule; g(0) alone is then evaluated, for the report.  The evaluations and the
+ * decisions between them all run on the device, queued at once: the host reads
+ * the outcome once, after the apply pass.
+ * Apply: X <- X(lambda); the index's CURRENT weights become w(lambda) on every
+ * real edge — the state cpd_index_set_weights(w') leaves (padding slots are
+ * copied unchanged; the search's incumbent tables are rebuilt at the next
+ * search, as after cpd_index_weights_from_loads); cpd_index_set_weights(ix,
+ * NULL) still restores free flow and leaves the flow table as it is.
+ * No flow table resident: the step initialises X = Y << 16 whatever lambda_q16
+ * says and reports lambda = 65536, evals = 0, g0 = 0, xw0 = 0 (from X = 0
+ * every D is >= 0 and the rule would answer 0).
+ * The exact relative gap before a step is -g0 / xw0 — total time on the
+ * current flow minus the time of the all-or-nothing loading, over the former,
+ * both under the current flow's weights: the caller forms it from ONE record.
+ * CPD_E_ARG, naming the value: no resident load table, or a sliced or timed
+ * one; an incomplete index; capacity NULL or some capacity 0; f out of range
+ * (load_div is ignored); lambda_q16 in 65537..0xFFFFFFFE; cpd_index_flow_fetch
+ * without a resident flow table.  On every error the flow table, the weights
+ * and the load table are untouched.
+ * cpd_index_flow_fetch: X in original edge order (m values, Q16), permuted on
+ * the GPU and copied out once.  cpd_index_flow_clear drops the table.         */
+#define CPD_STEP_LINE 0xFFFFFFFFu
+typedef struct cpd_flow_info {
+    uint32_t lambda_q16;        /* the step taken */
+    uint32_t evals;             /* evaluations of g made */
+    uint64_t g0_lo, g0_hi;      /* g(0), signed 128: minus the gap's numerator, Q16 */
+    uint64_t xw0_lo, xw0_hi;    /* sum of X * w(0), unsigned 128, Q16: the gap's denominator */
+    uint64_t tstt_lo, tstt_hi;  /* after the step: sum of (X >> 16) * w', as cpd_vdf_info */
+    uint64_t changed;           /* edges with w' != w0 */
+    double   line_ms, apply_ms; /* device time of the evaluations / of the apply pass */
+} cpd_flow_info;
+int  cpd_index_flow_step(cpd_index* ix, const uint32_t* capacity /* m, edge order, >= 1 */,
+                         const cpd_vdf* f /* load_div ignored */,
+                         uint32_t lambda_q16 /* 0..65536 or CPD_STEP_LINE */,
+                         cpd_flow_info* info /* may be NULL */);
+int  cpd_index_flow_fetch(cpd_index* ix, uint64_t* flow /* m, edge order, Q16 */);
+int  cpd_index_flow_clear(cpd_index* ix);
+
+/* cpd_query_assign with the line rule.  The flow table is cleared first (once
+ * the first loading has succeeded: an error of iteration 1 changes nothing).
+ * Iteration k = 1 .. iters:
+ *   1. cpd_query_search_loads(opts, prefix_bytes, demand, 0): a fresh
+ *      all-or-nothing loading Y under the current weights (iteration 1: the
+ *      weights the index holds, so a warm start works as in cpd_query_assign);
+ *   2. sptt_k as cpd_query_assign forms it;
+ *   3. cpd_index_flow_step(CPD_STEP_LINE): iteration 1 initialises X = Y << 16.
+ * The loop stops early after an iteration k >= 2 whose lambda is 0: the
+ * weights are unchanged, and a deterministic search would find the same
+ * routes and the same lambda again (this holds only without a wall-clock
+ * opts->time_ns).  *done = the records filled; the rest are zero.  The
+ * capacities are uploaded once.  Record k's -g0 / xw0 is the exact relative
+ * gap BEFORE step k; no partner record is needed.  Afterwards cpd_query_fetch
+ * and cpd_query_search_counters return the last iteration's search,
+ * cpd_query_loads_fetch its loading, cpd_index_flow_fetch the flow.  The
+ * prefix pool's CPD_E_OOM and the flow step's CPD_E_RANGE pass through from
+ * iteration 1 with nothing changed; in a later iteration the call stops there,
+ * the message naming the iteration, with the flow table and weights of the
+ * iterations that completed.  The empty batch is answered: the flow table
+ * zeroed, w0 on every edge, *done = 1 and that record's counts all zero apart
+ * from lambda_q16 = 65536, what the initialising step reports.  CPD_E_ARG as
+ * cpd_query_assign, and for a NULL done.                                     */
+typedef struct cpd_assign_line_iter {
+    uint64_t finished;          /* as cpd_assign_iter */
+    uint64_t sptt_lo, sptt_hi;
+    uint64_t tstt_lo, tstt_hi;  /* cpd_flow_info's: the flow after the step under its weights */
+    uint64_t moves, changed;
+    double   search_ms, loads_ms, vdf_ms;  /* vdf_ms: the apply pass (+ the capacity upload in record 1) */
+    uint32_t lambda_q16, evals; /* as cpd_flow_info */
+    uint64_t g0_lo, g0_hi;
+    uint64_t xw0_lo, xw0_hi;
+    double   line_ms;
+} cpd_assign_line_iter;
+int  cpd_query_assign_line(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                           const uint32_t* demand /* nq, caller order; NULL = 1 each */,
+                           const uint32_t* capacity /* m, edge order, >= 1 */,
+                           const cpd_vdf* f /* load_div ignored */, uint32_t iters /* 1..65535 */,
+                           cpd_assign_line_iter* out /* iters records */,
+                           uint32_t* done /* records filled */);
 
 /* ------------------------------------------------------------------------ */
 /* [gpu] Per-kernel device timing (HIP events on the library's stream).      */
