@@ -39,6 +39,8 @@ MAX_LOAD_SLICES = 8
 LOADS_ACCUMULATE = 1
 TIMED_LOADS = 2
 STEP_LINE = 0xFFFFFFFF
+ALPHA_CONJ = 0xFFFFFFFF
+ALPHA_MAX = 64881
 
 EXPORTED = [
     "cpd_last_error", "cpd_version", "cpd_partition", "cpd_partition_nbuckets",
@@ -66,6 +68,7 @@ EXPORTED = [
     "cpd_index_weights_from_loads", "cpd_index_get_weights", "cpd_index_get_weight_sets",
     "cpd_query_assign",
     "cpd_index_flow_step", "cpd_index_flow_fetch", "cpd_index_flow_clear", "cpd_query_assign_line",
+    "cpd_index_flow_step_conj", "cpd_index_target_fetch", "cpd_query_assign_conj",
 ]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
@@ -152,6 +155,19 @@ class AssignLineIter(C.Structure):
     _fields_ = AssignIter._fields_ + [("lambda_q16", C.c_uint32), ("evals", C.c_uint32)] + \
                [(k, C.c_uint64) for k in ("g0_lo", "g0_hi", "xw0_lo", "xw0_hi")] + \
                [("line_ms", C.c_double)]
+
+
+class ConjInfo(C.Structure):
+    _fields_ = [("alpha_q16", C.c_uint32), ("lambda_q16", C.c_uint32), ("evals", C.c_uint32)] + \
+               [(k, C.c_uint64) for k in ("n_lo", "n_hi", "m_lo", "m_hi", "gy_lo", "gy_hi",
+                                          "xw0_lo", "xw0_hi", "g0_lo", "g0_hi", "tstt_lo",
+                                          "tstt_hi", "changed")] + \
+               [("conj_ms", C.c_double), ("line_ms", C.c_double), ("apply_ms", C.c_double)]
+
+
+class AssignConjIter(C.Structure):
+    _fields_ = AssignLineIter._fields_ + [("alpha_q16", C.c_uint32)] + \
+               [(k, C.c_uint64) for k in ("n_lo", "n_hi", "m_lo", "m_hi", "gy_lo", "gy_hi")]
 
 
 def _s128(lo: int, hi: int) -> int:
@@ -1174,6 +1190,86 @@ class Index:
                          "lambda_q16": r.lambda_q16, "evals": r.evals,
                          "g0": _s128(r.g0_lo, r.g0_hi), "xw0": (r.xw0_hi << 64) | r.xw0_lo,
                          "line_ms": r.line_ms})
+        return recs
+
+    @staticmethod
+    def _alpha(alpha) -> int:
+        return ALPHA_CONJ if alpha == "conj" else int(alpha) & 0xFFFFFFFF
+
+    def flow_step_conj(self, capacity, alpha="conj", lam="line", a=(3, 20), power: int = 4) -> dict:
+        """One conjugate step towards the resident one-plane load table
+        (cpd_index_flow_step_conj, cpd_api.h "The conjugate step"): alpha =
+        "conj" for the rule or a value in 0..ALPHA_MAX (Q16), lam as
+        flow_step's.  Returns alpha_q16, lambda_q16, evals, n, gy and g0
+        (signed Python ints), m, xw0 and tstt (Python ints), changed, conj_ms,
+        line_ms, apply_ms; the relative gap before the step is -gy / xw0."""
+        c = self._capacity(capacity)
+        f = Vdf(int(a[0]), int(a[1]), int(power), 1)
+        info = ConjInfo()
+        _check(lib.cpd_index_flow_step_conj(self._h, _ptr(c, u32p), C.byref(f),
+                                            C.c_uint32(self._alpha(alpha)),
+                                            C.c_uint32(self._lambda(lam)), C.byref(info)))
+        return {"alpha_q16": info.alpha_q16, "lambda_q16": info.lambda_q16, "evals": info.evals,
+                "n": _s128(info.n_lo, info.n_hi), "m": (info.m_hi << 64) | info.m_lo,
+                "gy": _s128(info.gy_lo, info.gy_hi), "xw0": (info.xw0_hi << 64) | info.xw0_lo,
+                "g0": _s128(info.g0_lo, info.g0_hi),
+                "tstt": (info.tstt_hi << 64) | info.tstt_lo, "changed": info.changed,
+                "conj_ms": info.conj_ms, "line_ms": info.line_ms, "apply_ms": info.apply_ms}
+
+    def target_fetch(self) -> np.ndarray:
+        """The target table, u64[m] in original edge order, Q16
+        (cpd_index_target_fetch): the point the last conjugate step aimed at."""
+        x = np.empty(self.graph.plan.info()["m"], np.uint64)
+        _check(lib.cpd_index_target_fetch(self._h, _ptr(x, u64p)))
+        return x
+
+    def assign_conj(self, s, t, capacity, iters: int, demand=None, a=(3, 20), power: int = 4,
+                    **search_opts):
+        """assign_line() with the conjugate step (cpd_query_assign_conj): one
+        dict per iteration made, holding assign_line()'s keys (g0 along S - X)
+        and alpha_q16, n, m, gy; the gap before step k is -gy / xw0.
+        Afterwards target_fetch() returns the last target."""
+        self.prepare(s, t)
+        return self.assign_conj_run(capacity, iters, demand, a, power, **search_opts)
+
+    def assign_conj_run(self, capacity, iters: int, demand=None, a=(3, 20), power: int = 4,
+                        prefix_bytes=0, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
+                        capacity_cols=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,
+                        capacity_max=0):
+        """cpd_query_assign_conj on the prepared queries (capacity_cols as in
+        assign_run)."""
+        self._path_offsets = None
+        c = self._capacity(capacity)
+        d = None
+        if demand is not None:
+            d = _u32(demand)
+            if d.shape != (self._nq,):
+                raise ValueError("demand must have one entry per prepared query")
+        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
+                       int(capacity_cols), int(virtual_tick_ns), SEARCH_FORMS[tables],
+                       float(workspace_frac), int(capacity_max))
+        f = Vdf(int(a[0]), int(a[1]), int(power), 1)
+        n = max(0, min(int(iters), 65535))
+        out = (AssignConjIter * max(1, n))()
+        done = C.c_uint32()
+        rc = lib.cpd_query_assign_conj(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)),
+                                       _ptr(d, u32p), _ptr(c, u32p), C.byref(f),
+                                       C.c_uint32(int(iters) & 0xFFFFFFFF), out, C.byref(done))
+        if rc == CPD_OK or (rc in (CPD_E_OOM, CPD_E_RANGE)
+                            and "iteration" in lib.cpd_last_error().decode()):
+            self._load_slices = 1  # a loading is resident
+        _check(rc)
+        recs = []
+        for r in out[:done.value]:
+            recs.append({"finished": r.finished, "sptt": (r.sptt_hi << 64) | r.sptt_lo,
+                         "tstt": (r.tstt_hi << 64) | r.tstt_lo, "moves": r.moves,
+                         "changed": r.changed, "search_ms": r.search_ms,
+                         "loads_ms": r.loads_ms, "vdf_ms": r.vdf_ms,
+                         "lambda_q16": r.lambda_q16, "evals": r.evals,
+                         "g0": _s128(r.g0_lo, r.g0_hi), "xw0": (r.xw0_hi << 64) | r.xw0_lo,
+                         "line_ms": r.line_ms, "alpha_q16": r.alpha_q16,
+                         "n": _s128(r.n_lo, r.n_hi), "m": (r.m_hi << 64) | r.m_lo,
+                         "gy": _s128(r.gy_lo, r.gy_hi)})
         return recs
 
     def __del__(self):

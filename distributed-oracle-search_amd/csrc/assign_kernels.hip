@@ -178,6 +178,8 @@ __device__ __forceinline__ unsigned long long flow_at(unsigned long long X, long
 // per slot, grid-stride.  Slots with D == 0 add nothing to g and skip the
 // delay function.  first != 0 (the lambda = 0 pass): also the sum of X * w(0)
 // into st[kFlowXw] and the largest counter of Y into st[kFlowMaxY].
+// Q16T: Y is a target table already in Q16 (the conjugate step's S), D = Y - X.
+template <bool Q16T>
 __global__ __launch_bounds__(256) void flow_line_eval(const unsigned long long* __restrict__ Y,
                                                       const unsigned long long* __restrict__ X,
                                                       const uint2* __restrict__ adj_free,
@@ -195,7 +197,7 @@ __global__ __launch_bounds__(256) void flow_line_eval(const unsigned long long* 
         const unsigned long long y = Y[i], x = X[i];
         if (first && y > ymax) ymax = y;
         // wraps for a counter the range check refuses: the sums are then unused
-        const long long d = (long long)((y << 16) - x);
+        const long long d = (long long)((Q16T ? y : y << 16) - x);
         if (d == 0 && !(first && x)) continue;
         const uint2 a = adj_free[i];
         if (a.x == 0xFFFFFFFFu) continue;  // padding: Y and X are 0 there anyway
@@ -268,6 +270,8 @@ __global__ __launch_bounds__(64) void flow_line_decide(uint32_t want,
 // X <- X(lambda) and the selected adjacency <- (dst, w(lambda)) with the
 // record's lambda; padding slots are copied from adj_free, their X left alone.
 // The sum of (X >> 16) * w' and the changed count as vdf_update<0> forms them.
+// Q16T as flow_line_eval's.
+template <bool Q16T>
 __global__ __launch_bounds__(256) void flow_apply(const unsigned long long* __restrict__ Y,
                                                   unsigned long long* __restrict__ X,
                                                   const uint2* __restrict__ adj_free,
@@ -285,7 +289,8 @@ __global__ __launch_bounds__(256) void flow_apply(const unsigned long long* __re
         uint2 a = adj_free[i];
         if (a.x != 0xFFFFFFFFu) {
             const unsigned long long x = X[i];
-            const long long d = (long long)((Y[i] << 16) - x);
+            const unsigned long long y = Y[i];
+            const long long d = (long long)((Q16T ? y : y << 16) - x);
             const unsigned long long xn = d ? flow_at(x, d, lam) : x;
             if (xn != x) X[i] = xn;
             const uint32_t w = vdf_weight(a.y, xn >> 16, cap_slot[i], f);
@@ -296,6 +301,159 @@ __global__ __launch_bounds__(256) void flow_apply(const unsigned long long* __re
         adj_out[i] = a;
     }
     wave_sum128(sum, changed, st + kFlowTstt);
+}
+
+// --- the conjugate step (cpd_api.h "The conjugate step") --------------------
+
+// The slope h of the delay function at volume x, Q16 per unit volume,
+// saturating.  r <= 2^20, q <= 2^28, t < 2^44, t * a_num * power < 2^62, and u
+// < c << 16 < 2^48 where it is shifted.
+__device__ __forceinline__ uint32_t vdf_slope(uint32_t w0, unsigned long long x, uint32_t c,
+                                              const cpd_vdf& f) {
+    const unsigned long long r =
+        x >= ((unsigned long long)c << 4) ? (1ull << 20) : (x << 16) / c;
+    unsigned long long q = f.power == 1u ? (1ull << 16) : r;
+    for (uint32_t i = 2; i < f.power; ++i) q = (q * r) >> 16;
+    const unsigned long long t = ((unsigned long long)w0 * q) >> 16;
+    const unsigned long long u = t * f.a_num * f.power / f.a_den;
+    return u >= ((unsigned long long)c << 16) ? 0xFFFFFFFFu : (uint32_t)((u << 16) / c);
+}
+
+// a += sign * |p| * |q| * h mod 2^128: the product of the magnitudes is kept in
+// two halves before h multiplies it (below 2^92 in the header's range)
+__device__ __forceinline__ void mad128_pqh(U128& a, long long p, long long q,
+                                           unsigned long long h) {
+    const unsigned long long mp = p < 0 ? 0ull - (unsigned long long)p : (unsigned long long)p;
+    const unsigned long long mq = q < 0 ? 0ull - (unsigned long long)q : (unsigned long long)q;
+    const unsigned long long plo = mp * mq, phi = __umul64hi(mp, mq);
+    unsigned long long lo = plo * h, hi = __umul64hi(plo, h) + phi * h;
+    if ((p < 0) != (q < 0)) {  // minus (hi, lo)
+        lo = 0ull - lo;
+        hi = ~hi + (lo == 0ull ? 1ull : 0ull);
+    }
+    add128(a, lo, hi);
+}
+
+// The step's four sums and the largest counter of Y: a lane per slot,
+// grid-stride.  S == nullptr: no target table is resident, S is X, and N and M
+// stay 0.  Slots with db == 0 skip the slope.
+__global__ __launch_bounds__(256) void conj_sums(const unsigned long long* __restrict__ Y,
+                                                 const unsigned long long* __restrict__ X,
+                                                 const unsigned long long* __restrict__ S,
+                                                 const uint2* __restrict__ adj_free,
+                                                 const uint32_t* __restrict__ cap_slot,
+                                                 unsigned long long nslots, cpd_vdf f,
+                                                 unsigned long long* __restrict__ st) {
+    U128 n{0ull, 0ull}, m{0ull, 0ull}, gy{0ull, 0ull}, xw{0ull, 0ull};
+    unsigned long long ymax = 0;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < nslots; i += step) {
+        const unsigned long long y = Y[i], x = X[i];
+        if (y > ymax) ymax = y;
+        // wraps for a counter the range check refuses: the sums are then unused
+        const long long dy = (long long)((y << 16) - x);
+        const long long ds = S ? (long long)(S[i] - x) : 0ll;
+        if (dy == 0 && ds == 0 && x == 0ull) continue;
+        const uint2 a = adj_free[i];
+        if (a.x == 0xFFFFFFFFu) continue;  // padding: Y, X and S are 0 there anyway
+        const uint32_t c = cap_slot[i];
+        const long long db = ds >> 16, df = dy >> 16;  // arithmetic: the floor
+        if (db) {
+            const unsigned long long h = vdf_slope(a.y, x >> 16, c, f);
+            mad128_pqh(n, db, df, h);
+            mad128_pqh(m, db, db, h);
+        }
+        const uint32_t w = vdf_weight(a.y, x >> 16, c, f);
+        mad128_signed(gy, dy, w);
+        mad128(xw, x, w);
+    }
+    wave_sum128(n, 0ull, st + kConjN);
+    wave_sum128(m, 0ull, st + kConjM);
+    wave_sum128(gy, 0ull, st + kConjGy);
+    wave_sum128(xw, 0ull, st + kFlowXw);
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long o = __shfl_down(ymax, d, 64);
+        ymax = o > ymax ? o : ymax;
+    }
+    if ((threadIdx.x & 63u) == 0u && ymax) atomicMax(&st[kFlowMaxY], ymax);
+}
+
+__device__ __forceinline__ U128 neg128(U128 a) {
+    U128 r{0ull - a.lo, ~a.hi};
+    if (r.lo == 0ull) ++r.hi;
+    return r;
+}
+
+__device__ __forceinline__ bool ge128(const U128& a, const U128& b) {
+    return a.hi != b.hi ? a.hi > b.hi : a.lo >= b.lo;
+}
+
+__device__ __forceinline__ U128 sub128(U128 a, const U128& b) {
+    const unsigned long long borrow = a.lo < b.lo ? 1ull : 0ull;
+    a.lo -= b.lo;
+    a.hi -= b.hi + borrow;
+    return a;
+}
+
+// One lane: refuses the step (st[kFlowDone] = 2) for a counter of Y at or
+// above 2^30, else alpha from the sums by the header's rule (want ==
+// CPD_ALPHA_CONJ) or the caller's.  The quotient is 16 shift-and-subtract
+// steps on the magnitudes: |N| < |Dn| < 2^127 there, so the doubled remainder
+// fits.  Plain stores from lane 0.
+__global__ __launch_bounds__(64) void conj_decide(uint32_t want,
+                                                  unsigned long long* __restrict__ st) {
+    if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+    if (st[kFlowMaxY] >= (1ull << 30)) {
+        st[kFlowDone] = 2ull;  // refused: nothing is written
+        return;
+    }
+    unsigned long long alpha = want;
+    if (want == CPD_ALPHA_CONJ) {
+        U128 n{st[kConjN], st[kConjN + 1]};
+        U128 dn = sub128(n, U128{st[kConjM], st[kConjM + 1]});
+        const bool nneg = (long long)n.hi < 0, dneg = (long long)dn.hi < 0;
+        alpha = 0ull;
+        if ((dn.lo | dn.hi) != 0ull && (n.lo | n.hi) != 0ull && nneg == dneg) {
+            if (nneg) n = neg128(n);
+            if (dneg) dn = neg128(dn);
+            if (ge128(n, dn)) {
+                alpha = CPD_ALPHA_MAX;
+            } else {
+                U128 rem = n;
+                for (int i = 0; i < 16; ++i) {
+                    rem.hi = (rem.hi << 1) | (rem.lo >> 63);
+                    rem.lo <<= 1;
+                    alpha <<= 1;
+                    if (ge128(rem, dn)) {
+                        rem = sub128(rem, dn);
+                        alpha |= 1ull;
+                    }
+                }
+                if (alpha > CPD_ALPHA_MAX) alpha = CPD_ALPHA_MAX;
+            }
+        }
+    }
+    st[kConjAlpha] = alpha;
+}
+
+// S <- Yq + floor(alpha * (S - Yq) / 2^16) on every slot once conj_decide has
+// accepted the range; S_old == nullptr: no target table was resident, the old
+// target is X.  Padding slots hold 0 in all three tables and get 0.
+__global__ __launch_bounds__(256) void conj_target(const unsigned long long* __restrict__ Y,
+                                                   const unsigned long long* __restrict__ X,
+                                                   const unsigned long long* S_old,
+                                                   unsigned long long* S, unsigned long long nslots,
+                                                   const unsigned long long* __restrict__ st) {
+    if (st[kFlowDone] != 0ull) return;
+    const unsigned long long alpha = st[kConjAlpha];
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < nslots; i += step) {
+        const unsigned long long yq = Y[i] << 16;
+        const unsigned long long so = S_old ? S_old[i] : X[i];
+        S[i] = flow_at(yq, (long long)(so - yq), alpha);
+    }
 }
 
 }  // namespace kern
@@ -354,12 +512,17 @@ void launch_sptt_reduce(const uint64_t* cost, const uint8_t* fin, const uint32_t
 
 void launch_flow_line_eval(const uint64_t* Y, const uint64_t* X, const uint32_t* adj_free,
                            const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f, bool first,
-                           unsigned long long* st, hipStream_t s) {
-    hipLaunchKernelGGL(kern::flow_line_eval, dim3(stride_grid(nslots)), dim3(256), 0, s,
-                       reinterpret_cast<const unsigned long long*>(Y),
-                       reinterpret_cast<const unsigned long long*>(X),
-                       reinterpret_cast<const uint2*>(adj_free), cap_slot, nslots, f,
-                       first ? 1u : 0u, st);
+                           unsigned long long* st, hipStream_t s, bool q16_target) {
+    const auto* y = reinterpret_cast<const unsigned long long*>(Y);
+    const auto* x = reinterpret_cast<const unsigned long long*>(X);
+    const auto* af = reinterpret_cast<const uint2*>(adj_free);
+    const dim3 grid(stride_grid(nslots)), blk(256);
+    if (q16_target)
+        hipLaunchKernelGGL(kern::flow_line_eval<true>, grid, blk, 0, s, y, x, af, cap_slot, nslots,
+                           f, first ? 1u : 0u, st);
+    else
+        hipLaunchKernelGGL(kern::flow_line_eval<false>, grid, blk, 0, s, y, x, af, cap_slot, nslots,
+                           f, first ? 1u : 0u, st);
 }
 
 void launch_flow_line_decide(uint32_t want, unsigned long long* st, hipStream_t s) {
@@ -368,12 +531,41 @@ void launch_flow_line_decide(uint32_t want, unsigned long long* st, hipStream_t 
 
 void launch_flow_apply(const uint64_t* Y, uint64_t* X, const uint32_t* adj_free,
                        const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f, uint32_t* adj_out,
-                       unsigned long long* st, hipStream_t s) {
-    hipLaunchKernelGGL(kern::flow_apply, dim3(stride_grid(nslots)), dim3(256), 0, s,
+                       unsigned long long* st, hipStream_t s, bool q16_target) {
+    const auto* y = reinterpret_cast<const unsigned long long*>(Y);
+    auto* x = reinterpret_cast<unsigned long long*>(X);
+    const auto* af = reinterpret_cast<const uint2*>(adj_free);
+    auto* ao = reinterpret_cast<uint2*>(adj_out);
+    const dim3 grid(stride_grid(nslots)), blk(256);
+    if (q16_target)
+        hipLaunchKernelGGL(kern::flow_apply<true>, grid, blk, 0, s, y, x, af, cap_slot, nslots, f,
+                           ao, st);
+    else
+        hipLaunchKernelGGL(kern::flow_apply<false>, grid, blk, 0, s, y, x, af, cap_slot, nslots, f,
+                           ao, st);
+}
+
+void launch_conj_sums(const uint64_t* Y, const uint64_t* X, const uint64_t* S,
+                      const uint32_t* adj_free, const uint32_t* cap_slot, uint64_t nslots,
+                      cpd_vdf f, unsigned long long* st, hipStream_t s) {
+    hipLaunchKernelGGL(kern::conj_sums, dim3(stride_grid(nslots)), dim3(256), 0, s,
                        reinterpret_cast<const unsigned long long*>(Y),
-                       reinterpret_cast<unsigned long long*>(X),
-                       reinterpret_cast<const uint2*>(adj_free), cap_slot, nslots, f,
-                       reinterpret_cast<uint2*>(adj_out), st);
+                       reinterpret_cast<const unsigned long long*>(X),
+                       reinterpret_cast<const unsigned long long*>(S),
+                       reinterpret_cast<const uint2*>(adj_free), cap_slot, nslots, f, st);
+}
+
+void launch_conj_decide(uint32_t want, unsigned long long* st, hipStream_t s) {
+    hipLaunchKernelGGL(kern::conj_decide, dim3(1), dim3(64), 0, s, want, st);
+}
+
+void launch_conj_target(const uint64_t* Y, const uint64_t* X, const uint64_t* S_old, uint64_t* S,
+                        uint64_t nslots, const unsigned long long* st, hipStream_t s) {
+    hipLaunchKernelGGL(kern::conj_target, dim3(stride_grid(nslots)), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long*>(Y),
+                       reinterpret_cast<const unsigned long long*>(X),
+                       reinterpret_cast<const unsigned long long*>(S_old),
+                       reinterpret_cast<unsigned long long*>(S), nslots, st);
 }
 
 }  // namespace cpd

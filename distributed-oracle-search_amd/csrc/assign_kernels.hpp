@@ -1,7 +1,8 @@
 // Host-callable launchers for the gfx950 kernels in assign_kernels.hip: the
 // slot-wise step from edge loads to weights (cpd_index_weights_from_loads),
 // the weights' way back to edge order (cpd_index_get_weights / _weight_sets)
-// and the demand-weighted cost sum of a search (cpd_query_assign).
+// the demand-weighted cost sum of a search (cpd_query_assign), the flow step
+// and the conjugate step.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
@@ -64,7 +65,14 @@ enum : uint32_t {
     kFlowEvals = 14,  // evaluations of g made
     kFlowG0 = 15,     // +0, +1: g(0)
     kFlowPhase = 17,  // 0: g(0) is next, 1: g(65536), 2: g(mid)
-    kFlowWords = 18
+    kFlowWords = 18,
+    // the conjugate step's words follow the flow step's (kFlowXw and kFlowMaxY
+    // are shared; kFlowDone == 2 there: a counter >= 2^30)
+    kConjN = 18,      // +0, +1: N (signed 128), +2 unused
+    kConjM = 21,      // +0, +1: M (unsigned 128), +2 unused
+    kConjGy = 24,     // +0, +1: gy (signed 128), +2 unused
+    kConjAlpha = 27,  // the alpha decided
+    kConjWords = 28
 };
 // launch_flow_line_eval: st[kFlowG ..] += the sum over the real slots of D *
 // w(lambda), D = (Y << 16) - X, lambda = st[kFlowLambda]; `first` (the lambda
@@ -78,12 +86,33 @@ enum : uint32_t {
 // launch_flow_apply: with st[kFlowDone] == 1, X <- X(lambda), adj_out <- (dst,
 // w(lambda)) per real slot (padding slots copied from adj_free), st[kFlowTstt
 // ..] += the sums; does nothing otherwise.
+// q16_target (eval and apply): Y is a target table already in Q16 (the
+// conjugate step's S), so D = Y - X; `first` is then never set.
 void launch_flow_line_eval(const uint64_t* Y, const uint64_t* X, const uint32_t* adj_free,
                            const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f, bool first,
-                           unsigned long long* st, hipStream_t s);
+                           unsigned long long* st, hipStream_t s, bool q16_target = false);
 void launch_flow_line_decide(uint32_t want, unsigned long long* st, hipStream_t s);
 void launch_flow_apply(const uint64_t* Y, uint64_t* X, const uint32_t* adj_free,
                        const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f, uint32_t* adj_out,
-                       unsigned long long* st, hipStream_t s);
+                       unsigned long long* st, hipStream_t s, bool q16_target = false);
+
+// The conjugate step (cpd_api.h "The conjugate step"), over the same state
+// array grown to kConjWords, queued before the line search's pairs:
+// launch_conj_sums: st[kConjN ..], st[kConjM ..], st[kConjGy ..], st[kFlowXw ..]
+// += the four sums over the real slots, st[kFlowMaxY] = the largest counter of
+// Y.  S: the target table (nslots u64, Q16), or nullptr when none is resident
+// (S = X: N and M stay 0).
+// launch_conj_decide: one lane; a counter >= 2^30 sets st[kFlowDone] = 2 (every
+// later kernel of the step then does nothing), else st[kConjAlpha] = the
+// header's rule over N and M (want == CPD_ALPHA_CONJ) or want itself.
+// launch_conj_target: with st[kFlowDone] == 0, S[i] = Yq + floor(alpha * (S_old
+// - Yq) / 2^16) on every slot; S_old may be S (in place) or nullptr (the old
+// target is X).
+void launch_conj_sums(const uint64_t* Y, const uint64_t* X, const uint64_t* S,
+                      const uint32_t* adj_free, const uint32_t* cap_slot, uint64_t nslots,
+                      cpd_vdf f, unsigned long long* st, hipStream_t s);
+void launch_conj_decide(uint32_t want, unsigned long long* st, hipStream_t s);
+void launch_conj_target(const uint64_t* Y, const uint64_t* X, const uint64_t* S_old, uint64_t* S,
+                        uint64_t nslots, const unsigned long long* st, hipStream_t s);
 
 }  // namespace cpd

@@ -422,6 +422,9 @@ struct cpd_rows {
 //                 of tables) is still served.
 struct cpd_index {
     cpd_graph* g = nullptr;
+    // g->device, kept here so that cpd_index_free never reads a graph that was
+    // freed first (a garbage collector finalises a cycle in any order)
+    int device = 0;
     uint32_t nrows = 0;   // rows when complete
     uint32_t added = 0;   // rows appended so far
     uint64_t total = 0;   // runs resident so far (keep_rle)
@@ -547,6 +550,11 @@ struct cpd_index {
     DevBuf<uint64_t> fl_tab, fl_out;
     DevBuf<unsigned long long> fl_st;
     bool flow_ready = false;
+    // the conjugate step (cpd_index_flow_step_conj, cpd_query_assign_conj):
+    // the target table S beside fl_tab, same layout; target_ready only after
+    // a conjugate step, dropped by cpd_index_flow_step and _flow_clear.
+    DevBuf<uint64_t> tg_tab;
+    bool target_ready = false;
 };
 
 template <class F>

@@ -15,6 +15,7 @@ std::unique_ptr<cpd_index> index_init(cpd_graph* g, const uint32_t* row_targets,
     CPD_REQUIRE(nrows == 0 || row_targets, CPD_E_ARG, "index: null row targets");
     auto ix = std::make_unique<cpd_index>();
     ix->g = g;
+    ix->device = g->device;
     ix->nrows = nrows;
     ix->row_of_col.assign(g->n, CPD_INF);
     if (nrows) ix->row_targets.assign(row_targets, row_targets + nrows);
@@ -1172,7 +1173,7 @@ int cpd_query_batch(cpd_index* ix, const uint32_t* s, const uint32_t* t, uint32_
 }
 
 void cpd_index_free(cpd_index* ix) {
-    if (ix && ix->g) (void)hipSetDevice(ix->g->device);
+    if (ix && ix->g) (void)hipSetDevice(ix->device);
     delete ix;
 }
 

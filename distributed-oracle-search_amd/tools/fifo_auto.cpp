@@ -14,7 +14,7 @@
 //                                           only: also write every edge's load)
 //             [--timed P [--loads]]  (table-search only: cost, and load, every
 //                                     move under the diff of its clock time)
-//             [--assign K --capacity C [--vdf A/B^P] [--step msa|line]]  (cpd-search
+//             [--assign K --capacity C [--vdf A/B^P] [--step msa|line|conj]]  (cpd-search
 //                                     only: K iterations of load and re-weight)
 //             [--verbose]  (per request on stderr: read+parse / prepare / compute)
 //
@@ -110,6 +110,11 @@
 // g0 xw0" (lambda in Q16, 0..65536; g0 signed; -g0 / xw0 is the relative gap
 // before step k), <query file>.loads the volumes X >> 16 of the final flow in
 // the same one-column format, and <query file>.diff the final weights as before.
+// --step conj answers through cpd_query_assign_conj (cpd_api.h "The conjugate
+// step"): .assign lines are "k finished sptt tstt moves changed lambda gy xw0
+// alpha" — the line form's columns with gy where g0 stood, so that minus
+// column 8 over column 9 is still the relative gap before step k, then alpha in
+// Q16 — and .loads and .diff are as with --step line.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -480,11 +485,14 @@ int main(int argc, char** argv) {
                      "file>.loads,\n"
                      "                  .assign (k finished sptt tstt moves changed) and .diff (the "
                      "final weights)\n"
-                     "       [--step msa|line]  with --assign: msa (default) as above; line answers "
+                     "       [--step msa|line|conj]  with --assign: msa (default) as above; line answers "
                      "through\n"
                      "                  cpd_query_assign_line (the line-search step): .assign lines "
                      "end in\n"
-                     "                  lambda g0 xw0, .loads holds the final flow's volumes\n");
+                     "                  lambda g0 xw0, .loads holds the final flow's volumes; conj "
+                     "answers through\n"
+                     "                  cpd_query_assign_conj (the conjugate step): .assign lines "
+                     "end in lambda gy xw0 alpha\n");
         return 2;
     }
     // table-search (make_fifos.py:20) or the CPD-heuristic search
@@ -584,11 +592,11 @@ int main(int argc, char** argv) {
         vdf = cpd_vdf{an, ad, pw, 1};
     }
     const std::string step = a.str("step", "msa");
-    if ((a.has("step") && !assign) || (step != "msa" && step != "line")) {
-        std::fprintf(stderr, "fifo_auto: --step msa|line needs --assign\n");
+    if ((a.has("step") && !assign) || (step != "msa" && step != "line" && step != "conj")) {
+        std::fprintf(stderr, "fifo_auto: --step msa|line|conj needs --assign\n");
         return 2;
     }
-    const bool step_line = step == "line";
+    const bool step_line = step == "line", step_conj = step == "conj";
     int mcode = cli::method_code(method);
     std::string xy = inputs[0];
     std::string outdir = a.str("outdir", ".");
@@ -927,6 +935,23 @@ int main(int argc, char** argv) {
                                         " " + std::to_string(r.lambda_q16) + " " +
                                         dec128_signed(r.g0_lo, r.g0_hi) + " " +
                                         dec128(r.xw0_lo, r.xw0_hi));
+                        search_ms += r.search_ms;
+                    }
+                    write_flow(ix, qfile, g);
+                } else if (step_conj) {
+                    std::vector<cpd_assign_conj_iter> it((size_t)assign_iters);
+                    uint32_t made = 0;
+                    rc = cpd_query_assign_conj(ix, &so, 0, nullptr, cap.data(), &vdf,
+                                               (uint32_t)assign_iters, it.data(), &made);
+                    if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+                    for (uint32_t k = 0; k < made; ++k) {
+                        const cpd_assign_conj_iter& r = it[k];
+                        lines.push_back(common(r.finished, r.sptt_lo, r.sptt_hi, r.tstt_lo, r.tstt_hi,
+                                               r.moves, r.changed) +
+                                        " " + std::to_string(r.lambda_q16) + " " +
+                                        dec128_signed(r.gy_lo, r.gy_hi) + " " +
+                                        dec128(r.xw0_lo, r.xw0_hi) + " " +
+                                        std::to_string(r.alpha_q16));
                         search_ms += r.search_ms;
                     }
                     write_flow(ix, qfile, g);

@@ -851,8 +851,8 @@ int  cpd_index_get_weight_sets(cpd_index* ix, uint32_t* nsets, uint32_t* w /* ns
  * Out of scope: a demand set larger than one prepared batch (write the loop
  * from cpd_query_search_loads(CPD_LOADS_ACCUMULATE) and
  * cpd_index_weights_from_loads(load_div), which is why both are public); a
- * time-dependent search; conjugate and bi-conjugate Frank-Wolfe (the line
- * search step is cpd_query_assign_line below).                              */
+ * time-dependent search; bi-conjugate Frank-Wolfe (the line search step is
+ * cpd_query_assign_line below, the conjugate step cpd_query_assign_conj).   */
 typedef struct cpd_assign_iter {
     uint64_t finished;          /* queries with finished == 1 in this iteration  */
     uint64_t sptt_lo, sptt_hi;  /* sum over those of demand[q] * cost[q], under the weights searched with */
@@ -971,6 +971,134 @@ int  cpd_query_assign_line(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
                            const uint32_t* capacity /* m, edge order, >= 1 */,
                            const cpd_vdf* f /* load_div ignored */, uint32_t iters /* 1..65535 */,
                            cpd_assign_line_iter* out /* iters records */,
+                           uint32_t* done /* records filled */);
+
+/* The conjugate step — the flow step towards a TARGET other than the new
+ * loading: a convex combination of the previous target and the new
+ * all-or-nothing loading, chosen conjugate to the previous direction under the
+ * Hessian of the objective (Mitradjieva and Lindberg's conjugate Frank-Wolfe).
+ * A plain Frank-Wolfe direction zig-zags; this costs two more slot-wise passes
+ * per step and no extra search.  A TARGET TABLE S is state of the index beside
+ * the flow table: one u64 per adjacency slot, Q16, in the flow table's order —
+ * the point the last step aimed at — carved from the arena as the flow table
+ * is.  It exists only after the calls of this section; cpd_index_flow_clear
+ * drops it with the flow table, and cpd_index_flow_step drops it too, since it
+ * moves X without knowing S.  cpd_query_loads_clear and cpd_index_set_weights
+ * leave it alone.
+ * A procedure, so that two implementations cannot disagree.  For a slot
+ * holding a real edge let Y be the resident one-plane load table and Yq = Y <<
+ * 16, X the flow and S the target; with no target table resident S is taken to
+ * be X.  w0, c and the delay function's parameters are as in the flow step.
+ * Range.  Every counter of Y must be below 2^30: CPD_E_RANGE otherwise, naming
+ * the first offending edge, with nothing changed.  Tighter than the flow
+ * step's 2^47, so that the sums below provably fit: when X and S were made by
+ * conjugate steps alone, |db|, |df| <= 2^30.
+ * The slope h of the delay function at x = X >> 16, Q16 per unit volume,
+ * saturating:
+ *     r   as in the delay function (Q16, clamped at 16.0)
+ *     q   = (power == 1) ? 1 << 16 : r;
+ *           repeat power - 2 times:  q = (q * r) >> 16              q <= 2^28
+ *     t   = (w0 * q) >> 16                                          t <  2^44
+ *     u   = (t * a_num * power) / a_den                       product <  2^62
+ *     h   = (u >= ((u64)c << 16)) ? 0xFFFFFFFF : (u << 16) / c
+ * All divisions truncate.  The clamp of r is ignored on purpose: the slope of
+ * the clamped function is 0 there, which would switch the conjugacy off
+ * exactly where congestion is worst.
+ * The sums, one pass over the slots:
+ *     db  = (S - X) >> 16        arithmetic shift: the floor, for negative
+ *     df  = (Yq - X) >> 16       values too
+ *     N   = sum of db * df * h           signed 128
+ *     M   = sum of db * db * h           unsigned 128
+ *     gy  = sum of (Yq - X) * w(0)       signed 128: minus the gap's numerator
+ *     xw0 = sum of X * w(0)              as the flow step
+ * Each term of N or M is below 2^92 in magnitude; fewer than 2^32 slots give
+ * less than 2^124, and N - M fits signed 128 bits.  Slots with db == 0 add
+ * nothing to N and M and skip h.  (After plain flow steps over larger counters
+ * the differences can be larger; the sums are then taken mod 2^128.)
+ * alpha (alpha_q16 == CPD_ALPHA_CONJ), with Dn = N - M:
+ *     Dn == 0, or N == 0, or N and Dn of opposite sign:   alpha = 0
+ *     else a = (|N| >= |Dn|) ? CPD_ALPHA_MAX : floor(|N| * 65536 / |Dn|)
+ *          alpha = min(a, CPD_ALPHA_MAX)
+ * CPD_ALPHA_MAX is 0.99 in Q16: the target never collapses onto the old one.
+ * An explicit alpha_q16 in 0..CPD_ALPHA_MAX skips the rule; the sums are still
+ * made and reported.  The division is 16 shift-and-subtract steps on 128-bit
+ * magnitudes in one lane of the device: |N| < |Dn| < 2^127 there, so the
+ * doubled remainder fits.
+ * New target.  S <- Yq + floor(alpha * (S - Yq) / 2^16), the product formed
+ * exactly and the floor toward minus infinity as in X(l).  alpha = 0 gives S =
+ * Yq, whatever S was.
+ * Line search and apply.  Exactly the flow step's with D = S - X (the new S) in
+ * place of (Y << 16) - X: the same line rule, an explicit lambda_q16 in
+ * 0..65536 or CPD_STEP_LINE; then X <- X(lambda), the current weights become
+ * w(lambda), tstt and changed are reported as there.  With alpha = 0 every
+ * value the step reports and writes equals what cpd_index_flow_step reports
+ * and writes from the same state, bit for bit, and gy == g0.
+ * No flow table resident: X and S are both initialised to Yq; the step reports
+ * alpha 0, lambda 65536, evals 0 and all sums 0.
+ * The sums, the alpha decision, the target pass, the 18 evaluate / decide pairs
+ * and the apply pass are queued at once; the host reads the outcome once.  The
+ * target pass writes S only after the decision has accepted the range.
+ * The exact relative gap before the step is -gy / xw0, from ONE record; g0 is
+ * g(0) along S - X and no longer the gap's numerator.
+ * CPD_E_ARG as the flow step, and for alpha_q16 in CPD_ALPHA_MAX + 1 ..
+ * 0xFFFFFFFE; cpd_index_target_fetch without a resident target table.  On
+ * every error X, S, the weights and the load table are untouched.
+ * cpd_index_target_fetch: S in original edge order, as cpd_index_flow_fetch
+ * reads X.                                                                   */
+#define CPD_ALPHA_CONJ 0xFFFFFFFFu
+#define CPD_ALPHA_MAX  64881u
+typedef struct cpd_conj_info {
+    uint32_t alpha_q16;         /* the alpha taken */
+    uint32_t lambda_q16;        /* the step taken */
+    uint32_t evals;             /* evaluations of g made */
+    uint64_t n_lo, n_hi;        /* N, signed 128 */
+    uint64_t m_lo, m_hi;        /* M, unsigned 128 */
+    uint64_t gy_lo, gy_hi;      /* gy, signed 128: minus the gap's numerator, Q16 */
+    uint64_t xw0_lo, xw0_hi;    /* sum of X * w(0), unsigned 128, Q16: the gap's denominator */
+    uint64_t g0_lo, g0_hi;      /* g(0) along S - X, after S is updated, signed 128 */
+    uint64_t tstt_lo, tstt_hi;  /* after the step: sum of (X >> 16) * w', as cpd_vdf_info */
+    uint64_t changed;           /* edges with w' != w0 */
+    double   conj_ms, line_ms, apply_ms; /* device time of the sums, decision and target pass /
+                                            of the evaluations / of the apply pass */
+} cpd_conj_info;
+int  cpd_index_flow_step_conj(cpd_index* ix, const uint32_t* capacity /* m, edge order, >= 1 */,
+                              const cpd_vdf* f /* load_div ignored */,
+                              uint32_t alpha_q16 /* 0..CPD_ALPHA_MAX or CPD_ALPHA_CONJ */,
+                              uint32_t lambda_q16 /* 0..65536 or CPD_STEP_LINE */,
+                              cpd_conj_info* info /* may be NULL */);
+int  cpd_index_target_fetch(cpd_index* ix, uint64_t* s /* m, edge order, Q16 */);
+
+/* cpd_query_assign_line with the conjugate step.  The flow and target tables
+ * are cleared first (once the first loading has succeeded).  Iteration k makes
+ * a fresh loading, forms sptt_k and runs cpd_index_flow_step_conj with
+ * CPD_STEP_LINE and alpha = CPD_ALPHA_CONJ, with one exception: after a record
+ * with lambda == 0 and alpha > 0 the conjugate direction went nowhere, and the
+ * next iteration passes alpha = 0 — a restart with a plain Frank-Wolfe step.
+ * The loop stops early after an iteration k >= 2 with lambda == 0 and alpha ==
+ * 0.  Error pass-through, the empty batch and *done are as
+ * cpd_query_assign_line; record k's -gy / xw0 is the exact relative gap before
+ * step k.  Afterwards cpd_index_target_fetch returns the last target.  A
+ * record is cpd_assign_line_iter's fields followed by alpha, n, m and gy.    */
+typedef struct cpd_assign_conj_iter {
+    uint64_t finished;          /* as cpd_assign_line_iter */
+    uint64_t sptt_lo, sptt_hi;
+    uint64_t tstt_lo, tstt_hi;
+    uint64_t moves, changed;
+    double   search_ms, loads_ms, vdf_ms;
+    uint32_t lambda_q16, evals;
+    uint64_t g0_lo, g0_hi;      /* as cpd_conj_info: along S - X */
+    uint64_t xw0_lo, xw0_hi;
+    double   line_ms;           /* the evaluations and the conjugate passes before them */
+    uint32_t alpha_q16;         /* as cpd_conj_info */
+    uint64_t n_lo, n_hi;
+    uint64_t m_lo, m_hi;
+    uint64_t gy_lo, gy_hi;
+} cpd_assign_conj_iter;
+int  cpd_query_assign_conj(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                           const uint32_t* demand /* nq, caller order; NULL = 1 each */,
+                           const uint32_t* capacity /* m, edge order, >= 1 */,
+                           const cpd_vdf* f /* load_div ignored */, uint32_t iters /* 1..65535 */,
+                           cpd_assign_conj_iter* out /* iters records */,
                            uint32_t* done /* records filled */);
 
 /* ------------------------------------------------------------------------ */
