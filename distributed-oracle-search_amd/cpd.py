@@ -170,10 +170,39 @@ class AssignConjIter(C.Structure):
                [(k, C.c_uint64) for k in ("n_lo", "n_hi", "m_lo", "m_hi", "gy_lo", "gy_hi")]
 
 
+def _u128(lo: int, hi: int) -> int:
+    """An unsigned 128-bit value from its two u64 halves."""
+    return (hi << 64) | lo
+
+
 def _s128(lo: int, hi: int) -> int:
     """A signed 128-bit value from its two u64 halves."""
-    v = (hi << 64) | lo
+    v = _u128(lo, hi)
     return v - (1 << 128) if hi >> 63 else v
+
+
+# The keys of an assignment loop's record, in the order of cpd_assign_conj_iter
+# (whose fields begin with cpd_assign_line_iter's, which begin with
+# cpd_assign_iter's): key, then kind — "plain" the field of that name, "u128" /
+# "s128" the value of its _lo and _hi halves.
+_ITER_KEYS = (("finished", "plain"), ("sptt", "u128"), ("tstt", "u128"), ("moves", "plain"),
+              ("changed", "plain"), ("search_ms", "plain"), ("loads_ms", "plain"),
+              ("vdf_ms", "plain"), ("lambda_q16", "plain"), ("evals", "plain"), ("g0", "s128"),
+              ("xw0", "u128"), ("line_ms", "plain"), ("alpha_q16", "plain"), ("n", "s128"),
+              ("m", "u128"), ("gy", "s128"))
+_ITER_NKEYS = {AssignIter: 8, AssignLineIter: 13, AssignConjIter: 17}  # the leading keys a type holds
+
+
+def _iter_dict(r) -> dict:
+    """One record of an assignment loop as a dict."""
+    d = {}
+    for key, kind in _ITER_KEYS[:_ITER_NKEYS[type(r)]]:
+        if kind == "plain":
+            d[key] = getattr(r, key)
+        else:
+            lo, hi = getattr(r, key + "_lo"), getattr(r, key + "_hi")
+            d[key] = _s128(lo, hi) if kind == "s128" else _u128(lo, hi)
+    return d
 
 
 class KernelTime(C.Structure):
@@ -220,6 +249,14 @@ def _ptr(a, ctype):
 
 def _u32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _search_opts(hscale, fscale, k_moves, itrs, time_ns, capacity, virtual_tick_ns, tables,
+                 workspace_frac, capacity_max) -> SearchOpts:
+    """cpd_search_opts from the search methods' keywords, in the struct's order."""
+    return SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
+                      int(capacity), int(virtual_tick_ns), SEARCH_FORMS[tables],
+                      float(workspace_frac), int(capacity_max))
 
 
 def version() -> str:
@@ -818,11 +855,7 @@ class Index:
         """cpd_query_loads on the prepared queries: stats (cost / hops /
         finished of this walk then come from cpd_query_fetch)."""
         self._path_offsets = None
-        d = None
-        if demand is not None:
-            d = _u32(demand)
-            if d.shape != (self._nq,):
-                raise ValueError("demand must have one entry per prepared query")
+        d = self._demand(demand)
         st = QueryStats()
         _check(lib.cpd_query_loads(self._h, C.c_int32(k_moves), _ptr(d, u32p), C.c_uint32(slices),
                                    C.c_uint32(slice_moves),
@@ -869,15 +902,12 @@ class Index:
         if period is None:
             raise ValueError("period is required")
         self._timed = False
-        dp = d = None
+        dp = None
         if depart is not None:
             dp = np.ascontiguousarray(depart, dtype=np.uint64)
             if dp.shape != (self._nq,):
                 raise ValueError("depart must have one entry per prepared query")
-        if demand is not None:
-            d = _u32(demand)
-            if d.shape != (self._nq,):
-                raise ValueError("demand must have one entry per prepared query")
+        d = self._demand(demand)
         flags = (TIMED_LOADS if loads else 0) | (LOADS_ACCUMULATE if accumulate else 0)
         st = QueryStats()
         _check(lib.cpd_query_timed(self._h, C.c_int32(k_moves), _ptr(dp, u64p),
@@ -909,9 +939,8 @@ class Index:
         (cost, plen, finished, counters[nq, 5], stats); finished = 2: the
         search outgrew its workspace (after the capacity_max reruns)."""
         self.prepare(s, t)
-        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
-                       int(capacity), int(virtual_tick_ns), SEARCH_FORMS[tables],
-                       float(workspace_frac), int(capacity_max))
+        o = _search_opts(hscale, fscale, k_moves, itrs, time_ns, capacity, virtual_tick_ns,
+                         tables, workspace_frac, capacity_max)
         st = SearchStats()
         _check(lib.cpd_query_search(self._h, C.byref(o), C.byref(st)))
         nq = len(s)
@@ -950,9 +979,8 @@ class Index:
         """cpd_query_search_paths on the prepared queries: (offsets u64[nq + 1],
         stats).  The offsets are kept: paths_fetch sizes its buffers from them."""
         self._path_offsets = None
-        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
-                       int(capacity), int(virtual_tick_ns), SEARCH_FORMS[tables],
-                       float(workspace_frac), int(capacity_max))
+        o = _search_opts(hscale, fscale, k_moves, itrs, time_ns, capacity, virtual_tick_ns,
+                         tables, workspace_frac, capacity_max)
         st = SearchStats()
         info = SearchPathsInfo()
         offsets = np.empty(self._nq + 1, np.uint64)
@@ -993,14 +1021,9 @@ class Index:
         """cpd_query_search_loads on the prepared queries: stats (flags: the
         call's flag word, instead of the one accumulate gives)."""
         self._path_offsets = None
-        d = None
-        if demand is not None:
-            d = _u32(demand)
-            if d.shape != (self._nq,):
-                raise ValueError("demand must have one entry per prepared query")
-        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
-                       int(capacity), int(virtual_tick_ns), SEARCH_FORMS[tables],
-                       float(workspace_frac), int(capacity_max))
+        d = self._demand(demand)
+        o = _search_opts(hscale, fscale, k_moves, itrs, time_ns, capacity, virtual_tick_ns,
+                         tables, workspace_frac, capacity_max)
         st = SearchStats()
         info = SearchLoadsInfo()
         if flags is None:
@@ -1032,6 +1055,14 @@ class Index:
             raise ValueError("capacity must have one entry per edge")
         return c
 
+    def _demand(self, demand):
+        if demand is None:
+            return None
+        d = _u32(demand)
+        if d.shape != (self._nq,):
+            raise ValueError("demand must have one entry per prepared query")
+        return d
+
     def weights_from_loads(self, capacity, a=(3, 20), power: int = 4, load_div: int = 1) -> dict:
         """The resident load table turned into weights in HBM
         (cpd_index_weights_from_loads) by the delay function of cpd_api.h: w' =
@@ -1047,7 +1078,7 @@ class Index:
                                                 C.byref(info)))
         if info.planes >= 2:
             self._nsets = info.planes
-        return {"tstt": (info.tstt_hi << 64) | info.tstt_lo, "changed": info.changed,
+        return {"tstt": _u128(info.tstt_lo, info.tstt_hi), "changed": info.changed,
                 "planes": info.planes, "vdf_ms": info.vdf_ms}
 
     def get_weights(self) -> np.ndarray:
@@ -1085,32 +1116,35 @@ class Index:
                    capacity_max=0):
         """cpd_query_assign on the prepared queries (capacity_cols: the
         search's `capacity` option, renamed beside the edge capacities)."""
+        return self._assign_loop(lib.cpd_query_assign, AssignIter, False, (CPD_E_OOM,), capacity,
+                                 iters, demand, a, power, prefix_bytes,
+                                 (hscale, fscale, k_moves, itrs, time_ns, capacity_cols,
+                                  virtual_tick_ns, tables, workspace_frac, capacity_max))
+
+    def _assign_loop(self, entry, record_type, with_done, resident_codes, capacity, iters,
+                     demand, a, power, prefix_bytes, search) -> list:
+        """One of the three loops on the prepared queries: `entry` over records
+        of `record_type`, one dict per record made (`with_done`: as many as the
+        entry point reports; else min(iters, 65535)).  resident_codes: the
+        errors after which, when they name an iteration, the completed
+        iterations have left a loading resident.  search: _search_opts'
+        arguments."""
         self._path_offsets = None
         c = self._capacity(capacity)
-        d = None
-        if demand is not None:
-            d = _u32(demand)
-            if d.shape != (self._nq,):
-                raise ValueError("demand must have one entry per prepared query")
-        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
-                       int(capacity_cols), int(virtual_tick_ns), SEARCH_FORMS[tables],
-                       float(workspace_frac), int(capacity_max))
+        d = self._demand(demand)
+        o = _search_opts(*search)
         f = Vdf(int(a[0]), int(a[1]), int(power), 1)
         n = max(0, min(int(iters), 65535))
-        out = (AssignIter * max(1, n))()
-        rc = lib.cpd_query_assign(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)),
-                                  _ptr(d, u32p), _ptr(c, u32p), C.byref(f),
-                                  C.c_uint32(int(iters) & 0xFFFFFFFF), out)
-        if rc == CPD_OK or (rc == CPD_E_OOM and "iteration" in lib.cpd_last_error().decode()):
-            self._load_slices = 1  # a table of the completed iterations is resident
+        out = (record_type * max(1, n))()
+        done = C.c_uint32()
+        rc = entry(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)), _ptr(d, u32p),
+                   _ptr(c, u32p), C.byref(f), C.c_uint32(int(iters) & 0xFFFFFFFF), out,
+                   *([C.byref(done)] if with_done else []))
+        if rc == CPD_OK or (rc in resident_codes
+                            and "iteration" in lib.cpd_last_error().decode()):
+            self._load_slices = 1  # a loading of the completed iterations is resident
         _check(rc)
-        recs = []
-        for r in out[:n]:
-            recs.append({"finished": r.finished, "sptt": (r.sptt_hi << 64) | r.sptt_lo,
-                         "tstt": (r.tstt_hi << 64) | r.tstt_lo, "moves": r.moves,
-                         "changed": r.changed, "search_ms": r.search_ms,
-                         "loads_ms": r.loads_ms, "vdf_ms": r.vdf_ms})
-        return recs
+        return [_iter_dict(r) for r in out[:done.value if with_done else n]]
 
     @staticmethod
     def _lambda(lam) -> int:
@@ -1129,8 +1163,8 @@ class Index:
         _check(lib.cpd_index_flow_step(self._h, _ptr(c, u32p), C.byref(f),
                                        C.c_uint32(self._lambda(lam)), C.byref(info)))
         return {"lambda_q16": info.lambda_q16, "evals": info.evals,
-                "g0": _s128(info.g0_lo, info.g0_hi), "xw0": (info.xw0_hi << 64) | info.xw0_lo,
-                "tstt": (info.tstt_hi << 64) | info.tstt_lo, "changed": info.changed,
+                "g0": _s128(info.g0_lo, info.g0_hi), "xw0": _u128(info.xw0_lo, info.xw0_hi),
+                "tstt": _u128(info.tstt_lo, info.tstt_hi), "changed": info.changed,
                 "line_ms": info.line_ms, "apply_ms": info.apply_ms}
 
     def flow_fetch(self) -> np.ndarray:
@@ -1160,37 +1194,11 @@ class Index:
                         capacity_max=0):
         """cpd_query_assign_line on the prepared queries (capacity_cols as in
         assign_run)."""
-        self._path_offsets = None
-        c = self._capacity(capacity)
-        d = None
-        if demand is not None:
-            d = _u32(demand)
-            if d.shape != (self._nq,):
-                raise ValueError("demand must have one entry per prepared query")
-        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
-                       int(capacity_cols), int(virtual_tick_ns), SEARCH_FORMS[tables],
-                       float(workspace_frac), int(capacity_max))
-        f = Vdf(int(a[0]), int(a[1]), int(power), 1)
-        n = max(0, min(int(iters), 65535))
-        out = (AssignLineIter * max(1, n))()
-        done = C.c_uint32()
-        rc = lib.cpd_query_assign_line(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)),
-                                       _ptr(d, u32p), _ptr(c, u32p), C.byref(f),
-                                       C.c_uint32(int(iters) & 0xFFFFFFFF), out, C.byref(done))
-        if rc == CPD_OK or (rc in (CPD_E_OOM, CPD_E_RANGE)
-                            and "iteration" in lib.cpd_last_error().decode()):
-            self._load_slices = 1  # a loading is resident
-        _check(rc)
-        recs = []
-        for r in out[:done.value]:
-            recs.append({"finished": r.finished, "sptt": (r.sptt_hi << 64) | r.sptt_lo,
-                         "tstt": (r.tstt_hi << 64) | r.tstt_lo, "moves": r.moves,
-                         "changed": r.changed, "search_ms": r.search_ms,
-                         "loads_ms": r.loads_ms, "vdf_ms": r.vdf_ms,
-                         "lambda_q16": r.lambda_q16, "evals": r.evals,
-                         "g0": _s128(r.g0_lo, r.g0_hi), "xw0": (r.xw0_hi << 64) | r.xw0_lo,
-                         "line_ms": r.line_ms})
-        return recs
+        return self._assign_loop(lib.cpd_query_assign_line, AssignLineIter, True,
+                                 (CPD_E_OOM, CPD_E_RANGE), capacity, iters, demand, a, power,
+                                 prefix_bytes,
+                                 (hscale, fscale, k_moves, itrs, time_ns, capacity_cols,
+                                  virtual_tick_ns, tables, workspace_frac, capacity_max))
 
     @staticmethod
     def _alpha(alpha) -> int:
@@ -1210,10 +1218,10 @@ class Index:
                                             C.c_uint32(self._alpha(alpha)),
                                             C.c_uint32(self._lambda(lam)), C.byref(info)))
         return {"alpha_q16": info.alpha_q16, "lambda_q16": info.lambda_q16, "evals": info.evals,
-                "n": _s128(info.n_lo, info.n_hi), "m": (info.m_hi << 64) | info.m_lo,
-                "gy": _s128(info.gy_lo, info.gy_hi), "xw0": (info.xw0_hi << 64) | info.xw0_lo,
+                "n": _s128(info.n_lo, info.n_hi), "m": _u128(info.m_lo, info.m_hi),
+                "gy": _s128(info.gy_lo, info.gy_hi), "xw0": _u128(info.xw0_lo, info.xw0_hi),
                 "g0": _s128(info.g0_lo, info.g0_hi),
-                "tstt": (info.tstt_hi << 64) | info.tstt_lo, "changed": info.changed,
+                "tstt": _u128(info.tstt_lo, info.tstt_hi), "changed": info.changed,
                 "conj_ms": info.conj_ms, "line_ms": info.line_ms, "apply_ms": info.apply_ms}
 
     def target_fetch(self) -> np.ndarray:
@@ -1238,39 +1246,11 @@ class Index:
                         capacity_max=0):
         """cpd_query_assign_conj on the prepared queries (capacity_cols as in
         assign_run)."""
-        self._path_offsets = None
-        c = self._capacity(capacity)
-        d = None
-        if demand is not None:
-            d = _u32(demand)
-            if d.shape != (self._nq,):
-                raise ValueError("demand must have one entry per prepared query")
-        o = SearchOpts(float(hscale), float(fscale), int(k_moves), int(itrs), int(time_ns),
-                       int(capacity_cols), int(virtual_tick_ns), SEARCH_FORMS[tables],
-                       float(workspace_frac), int(capacity_max))
-        f = Vdf(int(a[0]), int(a[1]), int(power), 1)
-        n = max(0, min(int(iters), 65535))
-        out = (AssignConjIter * max(1, n))()
-        done = C.c_uint32()
-        rc = lib.cpd_query_assign_conj(self._h, C.byref(o), C.c_uint64(int(prefix_bytes)),
-                                       _ptr(d, u32p), _ptr(c, u32p), C.byref(f),
-                                       C.c_uint32(int(iters) & 0xFFFFFFFF), out, C.byref(done))
-        if rc == CPD_OK or (rc in (CPD_E_OOM, CPD_E_RANGE)
-                            and "iteration" in lib.cpd_last_error().decode()):
-            self._load_slices = 1  # a loading is resident
-        _check(rc)
-        recs = []
-        for r in out[:done.value]:
-            recs.append({"finished": r.finished, "sptt": (r.sptt_hi << 64) | r.sptt_lo,
-                         "tstt": (r.tstt_hi << 64) | r.tstt_lo, "moves": r.moves,
-                         "changed": r.changed, "search_ms": r.search_ms,
-                         "loads_ms": r.loads_ms, "vdf_ms": r.vdf_ms,
-                         "lambda_q16": r.lambda_q16, "evals": r.evals,
-                         "g0": _s128(r.g0_lo, r.g0_hi), "xw0": (r.xw0_hi << 64) | r.xw0_lo,
-                         "line_ms": r.line_ms, "alpha_q16": r.alpha_q16,
-                         "n": _s128(r.n_lo, r.n_hi), "m": (r.m_hi << 64) | r.m_lo,
-                         "gy": _s128(r.gy_lo, r.gy_hi)})
-        return recs
+        return self._assign_loop(lib.cpd_query_assign_conj, AssignConjIter, True,
+                                 (CPD_E_OOM, CPD_E_RANGE), capacity, iters, demand, a, power,
+                                 prefix_bytes,
+                                 (hscale, fscale, k_moves, itrs, time_ns, capacity_cols,
+                                  virtual_tick_ns, tables, workspace_frac, capacity_max))
 
     def __del__(self):
         if getattr(self, "_h", None):

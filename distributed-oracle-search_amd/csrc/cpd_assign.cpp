@@ -1,12 +1,16 @@
 // Loads to weights in HBM and the loops around it (cpd_index_weights_from_loads,
-// cpd_index_get_weights / _weight_sets, cpd_query_assign; the flow step and the
-// conjugate step with cpd_query_assign_line / _assign_conj).
+// cpd_index_get_weights / _weight_sets; cpd_index_flow_step and _flow_step_conj
+// over one step routine; cpd_query_assign, _assign_line and _assign_conj over
+// one loop).
+#include <cstddef>
+
 #include "assign_kernels.hpp"
 #include "cpd_gpu_internal.hpp"
 
 namespace {
 
-// What the entry points check before anything is touched.
+// What the entry points check before anything is touched, each worded with
+// the caller's name.
 void check_vdf(const cpd_vdf* f, bool with_div, const char* who) {
     const std::string w(who);
     CPD_REQUIRE(f, CPD_E_ARG, w + ": null delay function");
@@ -25,6 +29,52 @@ void check_capacity(const cpd_index* ix, const uint32_t* capacity, const char* w
     for (uint32_t e = 0; e < ix->g->m; ++e)
         CPD_REQUIRE(capacity[e] != 0u, CPD_E_ARG,
                     w + ": capacity 0 on edge " + std::to_string(e) + " (each must be >= 1)");
+}
+
+void check_complete(const cpd_index* ix, const char* who) {
+    CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
+                std::string(who) + ": index incomplete (" + std::to_string(ix->added) + " of " +
+                    std::to_string(ix->nrows) + " rows appended)");
+}
+
+void check_lambda(uint32_t lambda_q16, const char* who) {
+    CPD_REQUIRE(lambda_q16 <= 65536u || lambda_q16 == CPD_STEP_LINE, CPD_E_ARG,
+                std::string(who) + ": lambda_q16 " + std::to_string(lambda_q16) +
+                    " is neither 0..65536 nor CPD_STEP_LINE");
+}
+
+void check_alpha(uint32_t alpha_q16, const char* who) {
+    CPD_REQUIRE(alpha_q16 <= CPD_ALPHA_MAX || alpha_q16 == CPD_ALPHA_CONJ, CPD_E_ARG,
+                std::string(who) + ": alpha_q16 " + std::to_string(alpha_q16) +
+                    " is neither 0..64881 nor CPD_ALPHA_CONJ");
+}
+
+void check_iters(uint32_t iters, const char* who) {
+    CPD_REQUIRE(iters >= 1u && iters <= 65535u, CPD_E_ARG,
+                std::string(who) + ": " + std::to_string(iters) + " iterations, 1 to 65535");
+}
+
+// What the flow step asks of the resident load table.
+void check_flow_table(const cpd_index* ix, const char* who) {
+    const std::string w(who);
+    CPD_REQUIRE(ix->loads_ready, CPD_E_ARG,
+                w + ": no load table resident (cpd_query_loads with nslices = 1 or "
+                    "cpd_query_search_loads first)");
+    CPD_REQUIRE(ix->ld_period == 0, CPD_E_ARG,
+                w + ": the resident load table is a timed walk's (period " +
+                    std::to_string(ix->ld_period) + "), the flow step needs one plane");
+    CPD_REQUIRE(ix->ld_slices == 1u, CPD_E_ARG,
+                w + ": the resident load table has " + std::to_string(ix->ld_slices) +
+                    " slices, the flow step needs one plane");
+}
+
+// One timed interval into the graph's aggregate of that name (timing runs).
+void add_agg(cpd_graph* g, const char* name, uint64_t launches, float ms, double bytes) {
+    if (!g->timing) return;
+    Agg& a = g->agg[name];
+    a.launches += launches;
+    a.ms += ms;
+    a.bytes += bytes;
 }
 
 // The capacities to slot order.  Uploaded and permuted on every call: 4 m
@@ -86,14 +136,9 @@ void apply_vdf(cpd_index* ix, const cpd_vdf& f, cpd_vdf_info* info) {
     }
     float ms = 0.f;
     HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    if (g->timing) {
-        // per slot and plane: a counter read, a weight written; per slot the
-        // free-flow pair and the capacity
-        Agg& ag = g->agg["vdf_update"];
-        ag.launches++;
-        ag.ms += ms;
-        ag.bytes += (double)nslots * (12.0 + 12.0 * planes);
-    }
+    // per slot and plane: a counter read, a weight written; per slot the
+    // free-flow pair and the capacity
+    add_agg(g, "vdf_update", 1, ms, (double)nslots * (12.0 + 12.0 * planes));
     if (info) {
         info->tstt_lo = h[0];
         info->tstt_hi = h[1];
@@ -120,254 +165,196 @@ void fetch_weights(cpd_index* ix, const uint32_t* src, uint32_t stride, uint32_t
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// What the flow step asks of the resident load table.
-void check_flow_table(const cpd_index* ix, const char* who) {
-    const std::string w(who);
-    CPD_REQUIRE(ix->loads_ready, CPD_E_ARG,
-                w + ": no load table resident (cpd_query_loads with nslices = 1 or "
-                    "cpd_query_search_loads first)");
-    CPD_REQUIRE(ix->ld_period == 0, CPD_E_ARG,
-                w + ": the resident load table is a timed walk's (period " +
-                    std::to_string(ix->ld_period) + "), the flow step needs one plane");
-    CPD_REQUIRE(ix->ld_slices == 1u, CPD_E_ARG,
-                w + ": the resident load table has " + std::to_string(ix->ld_slices) +
-                    " slices, the flow step needs one plane");
-}
-
-// A step refused by its decide kernel, nothing applied: names the first edge
-// whose counter is at or above 2^bits.
-[[noreturn]] void refuse_range(cpd_index* ix, const char* who, unsigned bits) {
-    cpd_graph* g = ix->g;
-    hipStream_t s = g->stream;
-    std::vector<uint64_t> loads(g->m);
-    ix->ld_out.alloc(g->m);
-    (void)hipGetLastError();
-    launch_loads_gather(ix->ld_tab.p, g->slot_of_edge_d.p, g->m, g->n << g->adj_shift, 1u,
-                        ix->ld_out.p, s);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(loads.data(), ix->ld_out.p, (size_t)g->m * sizeof(uint64_t),
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    uint32_t e = 0;
-    while (e < g->m && loads[e] < (1ull << bits)) ++e;
-    throw Error(CPD_E_RANGE, std::string(who) + ": load " +
-                                 std::to_string(e < g->m ? loads[e] : 0ull) + " on edge " +
-                                 std::to_string(e) + " (every counter must be below 2^" +
-                                 std::to_string(bits) + ")");
-}
-
-// The flow step over the resident one-plane table with the slot-order
-// capacities in place: every evaluate / decide pair of the line search and the
-// apply pass are queued at once; the host reads the state once, afterwards.
-void flow_step(cpd_index* ix, const cpd_vdf& f, uint32_t lambda_q16, cpd_flow_info* info) {
-    cpd_graph* g = ix->g;
-    hipStream_t s = g->stream;
-    const uint64_t nslots = (uint64_t)g->n << g->adj_shift;
-    const bool init = !ix->flow_ready;  // no flow table: X = Y << 16 whatever lambda says
-    {
-        ArenaScope carve;
-        ix->fl_tab.alloc((size_t)nslots);
-        ix->fl_st.alloc(kFlowWords);
-        ix->adj_sel.alloc((size_t)(2u * nslots));
-    }
-    if (init) HIP_CHECK(hipMemsetAsync(ix->fl_tab.p, 0, (size_t)nslots * sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(ix->fl_st.p, 0, kFlowWords * sizeof(unsigned long long), s));
-    const uint32_t want = init ? 65536u : lambda_q16;
-    const uint32_t pairs = want <= 65536u ? 1u : 18u;
-    Events<3> ev(g);
-    HIP_CHECK(hipEventRecord(ev.e[0], s));
-    (void)hipGetLastError();
-    for (uint32_t i = 0; i < pairs; ++i) {
-        launch_flow_line_eval(ix->ld_tab.p, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f,
-                              i == 0u, ix->fl_st.p, s);
-        launch_flow_line_decide(want, ix->fl_st.p, s);
-    }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[1], s));
-    launch_flow_apply(ix->ld_tab.p, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f,
-                      ix->adj_sel.p, ix->fl_st.p, s);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[2], s));
-    unsigned long long h[kFlowWords] = {};
-    HIP_CHECK(hipMemcpyAsync(h, ix->fl_st.p, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (h[kFlowDone] != 1ull) refuse_range(ix, "flow step", 47u);
-    ix->tg_tab.release();  // the step moved X without knowing S
-    ix->target_ready = false;
-    ix->flow_ready = true;
-    ix->custom_w = true;
-    ix->c_ready = false;  // the search's incumbent tables follow the weights
-    float line_ms = 0.f, apply_ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&line_ms, ev.e[0], ev.e[1]));
-    HIP_CHECK(hipEventElapsedTime(&apply_ms, ev.e[1], ev.e[2]));
-    if (g->timing) {
-        // per evaluation and slot: Y, X, the free-flow pair, the capacity (28
-        // B); the apply also writes X and the selected pair
-        Agg& ae = g->agg["flow_line_eval"];
-        ae.launches += h[kFlowEvals];
-        ae.ms += line_ms;
-        ae.bytes += (double)nslots * 28.0 * (double)h[kFlowEvals];
-        Agg& aa = g->agg["flow_apply"];
-        aa.launches++;
-        aa.ms += apply_ms;
-        aa.bytes += (double)nslots * 44.0;
-    }
-    if (info) {
-        *info = cpd_flow_info{};
-        info->lambda_q16 = (uint32_t)h[kFlowLambda];
-        if (!init) {  // the initialising step reports no evaluation
-            info->evals = (uint32_t)h[kFlowEvals];
-            info->g0_lo = h[kFlowG0];
-            info->g0_hi = h[kFlowG0 + 1];
-            info->xw0_lo = h[kFlowXw];
-            info->xw0_hi = h[kFlowXw + 1];
-        }
-        info->tstt_lo = h[kFlowTstt];
-        info->tstt_hi = h[kFlowTstt + 1];
-        info->changed = h[kFlowTstt + 2];
-        info->line_ms = line_ms;
-        info->apply_ms = apply_ms;
-    }
-}
-
-// The conjugate step, queued like the flow step: the sums, the alpha decision
-// and the target pass, then the line search and the apply pass against the
-// target table; the host reads the state once, afterwards.
-void conj_step(cpd_index* ix, const cpd_vdf& f, uint32_t alpha_q16, uint32_t lambda_q16,
-               cpd_conj_info* info) {
-    cpd_graph* g = ix->g;
-    hipStream_t s = g->stream;
-    const uint64_t nslots = (uint64_t)g->n << g->adj_shift;
-    // no flow table: X = 0, S = X, alpha = 0 and lambda = 65536 give X = S = Y << 16
-    const bool init = !ix->flow_ready;
-    const bool has_s = !init && ix->target_ready;
-    {
-        ArenaScope carve;
-        ix->fl_tab.alloc((size_t)nslots);
-        ix->tg_tab.alloc((size_t)nslots);
-        ix->fl_st.alloc(kConjWords);
-        ix->adj_sel.alloc((size_t)(2u * nslots));
-    }
-    if (init) HIP_CHECK(hipMemsetAsync(ix->fl_tab.p, 0, (size_t)nslots * sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(ix->fl_st.p, 0, kConjWords * sizeof(unsigned long long), s));
-    const uint32_t want = init ? 65536u : lambda_q16;
-    const uint32_t pairs = want <= 65536u ? 1u : 18u;
-    const uint64_t* s_old = has_s ? ix->tg_tab.p : nullptr;
-    Events<4> ev(g);
-    HIP_CHECK(hipEventRecord(ev.e[0], s));
-    (void)hipGetLastError();
-    launch_conj_sums(ix->ld_tab.p, ix->fl_tab.p, s_old, g->adj.p, ix->vdf_cap.p, nslots, f,
-                     ix->fl_st.p, s);
-    launch_conj_decide(init ? 0u : alpha_q16, ix->fl_st.p, s);
-    launch_conj_target(ix->ld_tab.p, ix->fl_tab.p, s_old, ix->tg_tab.p, nslots, ix->fl_st.p, s);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[1], s));
-    for (uint32_t i = 0; i < pairs; ++i) {
-        launch_flow_line_eval(ix->tg_tab.p, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f, false,
-                              ix->fl_st.p, s, true);
-        launch_flow_line_decide(want, ix->fl_st.p, s);
-    }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[2], s));
-    launch_flow_apply(ix->tg_tab.p, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f,
-                      ix->adj_sel.p, ix->fl_st.p, s, true);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[3], s));
-    unsigned long long h[kConjWords] = {};
-    HIP_CHECK(hipMemcpyAsync(h, ix->fl_st.p, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (h[kFlowDone] != 1ull) refuse_range(ix, "conjugate step", 30u);
-    ix->flow_ready = true;
-    ix->target_ready = true;
-    ix->custom_w = true;
-    ix->c_ready = false;  // the search's incumbent tables follow the weights
-    float conj_ms = 0.f, line_ms = 0.f, apply_ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&conj_ms, ev.e[0], ev.e[1]));
-    HIP_CHECK(hipEventElapsedTime(&line_ms, ev.e[1], ev.e[2]));
-    HIP_CHECK(hipEventElapsedTime(&apply_ms, ev.e[2], ev.e[3]));
-    if (g->timing) {
-        // the sums read Y, X, S, the free-flow pair and the capacity (36 B a
-        // slot), the target pass reads Y and S (or X) and writes S (24 B); an
-        // evaluation and the apply as the flow step's
-        Agg& ac = g->agg["conj_sums_target"];
-        ac.launches += 3;
-        ac.ms += conj_ms;
-        ac.bytes += (double)nslots * 60.0;
-        Agg& ae = g->agg["flow_line_eval"];
-        ae.launches += h[kFlowEvals];
-        ae.ms += line_ms;
-        ae.bytes += (double)nslots * 28.0 * (double)h[kFlowEvals];
-        Agg& aa = g->agg["flow_apply"];
-        aa.launches++;
-        aa.ms += apply_ms;
-        aa.bytes += (double)nslots * 44.0;
-    }
-    if (info) {
-        *info = cpd_conj_info{};
-        info->lambda_q16 = (uint32_t)h[kFlowLambda];
-        if (!init) {  // the initialising step reports no evaluation and no sums
-            info->alpha_q16 = (uint32_t)h[kConjAlpha];
-            info->evals = (uint32_t)h[kFlowEvals];
-            info->n_lo = h[kConjN];
-            info->n_hi = h[kConjN + 1];
-            info->m_lo = h[kConjM];
-            info->m_hi = h[kConjM + 1];
-            info->gy_lo = h[kConjGy];
-            info->gy_hi = h[kConjGy + 1];
-            info->xw0_lo = h[kFlowXw];
-            info->xw0_hi = h[kFlowXw + 1];
-            info->g0_lo = h[kFlowG0];
-            info->g0_hi = h[kFlowG0 + 1];
-        }
-        info->tstt_lo = h[kFlowTstt];
-        info->tstt_hi = h[kFlowTstt + 1];
-        info->changed = h[kFlowTstt + 2];
-        info->conj_ms = conj_ms;
-        info->line_ms = line_ms;
-        info->apply_ms = apply_ms;
-    }
-}
-
-// A flow-order table (the flow or the target) in edge order, permuted on the
-// GPU and copied out once.
-void fetch_slot_table(cpd_index* ix, const uint64_t* tab, uint64_t* out, const char* who) {
+// A one-plane slot-order table of u64 (the loads, the flow or the target) in
+// edge order, permuted on the GPU through `stage` and copied out once.
+void fetch_slot_table(cpd_index* ix, const uint64_t* tab, DevBuf<uint64_t>& stage, uint64_t* out,
+                      const char* who) {
     cpd_graph* g = ix->g;
     if (!g->m) return;
     CPD_REQUIRE(out, CPD_E_ARG, std::string(who) + ": null argument");
     g->select();
     hipStream_t s = g->stream;
-    ix->fl_out.alloc(g->m);
+    stage.alloc(g->m);
     (void)hipGetLastError();
-    launch_loads_gather(tab, g->slot_of_edge_d.p, g->m, g->n << g->adj_shift, 1u, ix->fl_out.p, s);
+    launch_loads_gather(tab, g->slot_of_edge_d.p, g->m, g->n << g->adj_shift, 1u, stage.p, s);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, ix->fl_out.p, (size_t)g->m * sizeof(uint64_t),
-                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(out, stage.p, (size_t)g->m * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                             s));
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// One round of the flow-table loops (cpd_query_assign_line, _assign_conj): a
-// fresh loading under the current weights, the capacities uploaded and the
-// flow state dropped once the first has succeeded, and sptt into h.
+// A step refused by its decide kernel, nothing applied: names the first edge
+// whose counter is at or above 2^bits.
+[[noreturn]] void refuse_range(cpd_index* ix, const char* who, unsigned bits) {
+    const uint32_t m = ix->g->m;
+    std::vector<uint64_t> loads(m);
+    fetch_slot_table(ix, ix->ld_tab.p, ix->ld_out, loads.data(), who);
+    uint32_t e = 0;
+    while (e < m && loads[e] < (1ull << bits)) ++e;
+    throw Error(CPD_E_RANGE, std::string(who) + ": load " +
+                                 std::to_string(e < m ? loads[e] : 0ull) + " on edge " +
+                                 std::to_string(e) + " (every counter must be below 2^" +
+                                 std::to_string(bits) + ")");
+}
+
+const char* step_name(bool conj) { return conj ? "conjugate step" : "flow step"; }
+
+// One step over the resident one-plane table Y with the slot-order capacities
+// in place, everything queued at once; the host reads the state once,
+// afterwards.  The plain step (cpd_index_flow_step) is the line search's
+// evaluate / decide pairs and the apply pass towards Y; it moves X without
+// knowing S, so the target table goes.  The conjugate step
+// (cpd_index_flow_step_conj) puts the sums, the alpha decision and the target
+// pass in front and runs the same pairs and pass towards the target table S,
+// over the state array grown to kConjWords.  *info: a plain step leaves
+// alpha, the sums and conj_ms 0.
+void flow_step(cpd_index* ix, const cpd_vdf& f, bool conj, uint32_t alpha_q16, uint32_t lambda_q16,
+               cpd_conj_info* info) {
+    cpd_graph* g = ix->g;
+    hipStream_t s = g->stream;
+    const uint64_t nslots = (uint64_t)g->n << g->adj_shift;
+    // no flow table: X = 0 and lambda = 65536 give X = Y << 16 whatever lambda
+    // says (conjugate: S = X and alpha = 0 as well, so X = S = Y << 16)
+    const bool init = !ix->flow_ready;
+    const bool has_s = conj && !init && ix->target_ready;
+    const uint32_t words = conj ? kConjWords : kFlowWords;
+    {
+        ArenaScope carve;
+        ix->fl_tab.alloc((size_t)nslots);
+        if (conj) ix->tg_tab.alloc((size_t)nslots);
+        ix->fl_st.alloc(words);
+        ix->adj_sel.alloc((size_t)(2u * nslots));
+    }
+    if (init) HIP_CHECK(hipMemsetAsync(ix->fl_tab.p, 0, (size_t)nslots * sizeof(uint64_t), s));
+    HIP_CHECK(hipMemsetAsync(ix->fl_st.p, 0, words * sizeof(unsigned long long), s));
+    const uint32_t want = init ? 65536u : lambda_q16;
+    const uint32_t pairs = want <= 65536u ? 1u : 18u;
+    const uint64_t* towards = conj ? ix->tg_tab.p : ix->ld_tab.p;  // Q16 when conj
+    Events<4> ev(g);  // conjugate passes | line search | apply; e[0] is the conjugate step's alone
+    (void)hipGetLastError();
+    if (conj) {
+        const uint64_t* s_old = has_s ? ix->tg_tab.p : nullptr;
+        HIP_CHECK(hipEventRecord(ev.e[0], s));
+        launch_conj_sums(ix->ld_tab.p, ix->fl_tab.p, s_old, g->adj.p, ix->vdf_cap.p, nslots, f,
+                         ix->fl_st.p, s);
+        launch_conj_decide(init ? 0u : alpha_q16, ix->fl_st.p, s);
+        launch_conj_target(ix->ld_tab.p, ix->fl_tab.p, s_old, ix->tg_tab.p, nslots, ix->fl_st.p, s);
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipEventRecord(ev.e[1], s));
+    for (uint32_t i = 0; i < pairs; ++i) {
+        // `first` (the lambda = 0 pass also sums X * w(0) and takes the largest
+        // Y) is the plain step's: conj_sums has done both
+        launch_flow_line_eval(towards, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f,
+                              !conj && i == 0u, ix->fl_st.p, s, conj);
+        launch_flow_line_decide(want, ix->fl_st.p, s);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[2], s));
+    launch_flow_apply(towards, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f, ix->adj_sel.p,
+                      ix->fl_st.p, s, conj);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[3], s));
+    // a plain step's alpha and sums read as 0: their words lie past the ones it copies
+    static_assert(kConjN >= kFlowWords && kConjAlpha >= kFlowWords, "conjugate words overlap");
+    unsigned long long h[kConjWords] = {};
+    HIP_CHECK(hipMemcpyAsync(h, ix->fl_st.p, words * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    // a counter at or above 2^47 (Y << 16 would pass 2^63) / 2^30 (the sums' terms)
+    if (h[kFlowDone] != 1ull) refuse_range(ix, step_name(conj), conj ? 30u : 47u);
+    if (!conj) ix->tg_tab.release();  // the step moved X without knowing S
+    ix->target_ready = conj;
+    ix->flow_ready = true;
+    ix->custom_w = true;
+    ix->c_ready = false;  // the search's incumbent tables follow the weights
+    float conj_ms = 0.f, line_ms = 0.f, apply_ms = 0.f;
+    if (conj) HIP_CHECK(hipEventElapsedTime(&conj_ms, ev.e[0], ev.e[1]));
+    HIP_CHECK(hipEventElapsedTime(&line_ms, ev.e[1], ev.e[2]));
+    HIP_CHECK(hipEventElapsedTime(&apply_ms, ev.e[2], ev.e[3]));
+    // the sums read Y, X, S, the free-flow pair and the capacity (36 B a slot),
+    // the target pass reads Y and S (or X) and writes S (24 B); per evaluation
+    // and slot: Y, X, the free-flow pair, the capacity (28 B); the apply also
+    // writes X and the selected pair
+    if (conj) add_agg(g, "conj_sums_target", 3, conj_ms, (double)nslots * 60.0);
+    add_agg(g, "flow_line_eval", h[kFlowEvals], line_ms,
+            (double)nslots * 28.0 * (double)h[kFlowEvals]);
+    add_agg(g, "flow_apply", 1, apply_ms, (double)nslots * 44.0);
+    *info = cpd_conj_info{};
+    info->lambda_q16 = (uint32_t)h[kFlowLambda];
+    if (!init) {  // the initialising step reports no evaluation and no sums
+        info->alpha_q16 = (uint32_t)h[kConjAlpha];
+        info->evals = (uint32_t)h[kFlowEvals];
+        info->n_lo = h[kConjN];
+        info->n_hi = h[kConjN + 1];
+        info->m_lo = h[kConjM];
+        info->m_hi = h[kConjM + 1];
+        info->gy_lo = h[kConjGy];
+        info->gy_hi = h[kConjGy + 1];
+        info->xw0_lo = h[kFlowXw];
+        info->xw0_hi = h[kFlowXw + 1];
+        info->g0_lo = h[kFlowG0];
+        info->g0_hi = h[kFlowG0 + 1];
+    }
+    info->tstt_lo = h[kFlowTstt];
+    info->tstt_hi = h[kFlowTstt + 1];
+    info->changed = h[kFlowTstt + 2];
+    info->conj_ms = conj_ms;
+    info->line_ms = line_ms;
+    info->apply_ms = apply_ms;
+}
+
+// cpd_index_flow_step / _flow_step_conj: the checks, the capacities, one step.
+void checked_step(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f, bool conj,
+                  uint32_t alpha_q16, uint32_t lambda_q16, cpd_conj_info* info) {
+    const char* who = step_name(conj);
+    CPD_REQUIRE(ix, CPD_E_ARG, std::string(who) + ": null index");
+    check_vdf(f, false, who);
+    if (conj) check_alpha(alpha_q16, who);
+    check_lambda(lambda_q16, who);
+    check_complete(ix, who);
+    check_flow_table(ix, who);
+    check_capacity(ix, capacity, who);
+    ix->g->select();
+    upload_capacity(ix, capacity);
+    flow_step(ix, *f, conj, alpha_q16, lambda_q16, info);
+}
+
+// The three rules of the assignment loop.
+enum class Rule { msa, line, conj };
+const char* const kLoopName[] = {"assign", "assign line", "assign conj"};
+
+// An error of iteration k >= 2: the k - 1 before it stand.
+Error iteration_failed(int code, Rule rule, uint32_t k, uint32_t iters, const std::string& why) {
+    return Error(code, std::string(kLoopName[(int)rule]) + ": iteration " + std::to_string(k) +
+                           " of " + std::to_string(iters) + " failed, the " +
+                           (rule == Rule::msa ? "table" : "flow table") +
+                           " and weights are those of " + std::to_string(k - 1) +
+                           " iterations: " + why);
+}
+
+// One round's loading: cpd_query_search_loads under the current weights — MSA
+// adds to the table of the rounds before (flags), the flow rules load afresh —
+// then, once the first has succeeded, the capacities uploaded (cap_ms) and for
+// the flow rules (reset_flow) the flow state dropped; sptt into h.
 void loading_round(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
-                   const uint32_t* demand, const uint32_t* capacity, uint32_t k, uint32_t iters,
-                   const std::string& who, cpd_search_stats& ss, cpd_search_loads_info& li,
-                   unsigned long long (&h)[3], float& cap_ms) {
+                   const uint32_t* demand, const uint32_t* capacity, Rule rule, uint32_t k,
+                   uint32_t iters, uint32_t flags, bool reset_flow, cpd_search_stats& ss,
+                   cpd_search_loads_info& li, unsigned long long (&h)[3], float& cap_ms) {
     cpd_graph* g = ix->g;
     hipStream_t s = g->stream;
     const uint32_t nq = ix->nq;
-    const int rc = cpd_query_search_loads(ix, opts, prefix_bytes, demand, 0u, &ss, &li);
+    const int rc = cpd_query_search_loads(ix, opts, prefix_bytes, demand, flags, &ss, &li);
     if (rc != CPD_OK) {
         const std::string why = cpd_last_error();
         if (k == 1) throw Error(rc, why);  // nothing has changed
-        throw Error(rc, who + ": iteration " + std::to_string(k) + " of " + std::to_string(iters) +
-                            " failed, the flow table and weights are those of " +
-                            std::to_string(k - 1) + " iterations: " + why);
+        throw iteration_failed(rc, rule, k, iters, why);
     }
     if (k == 1) {
-        // the loop starts from an empty flow table; the capacities are
-        // uploaded once, after the first loading succeeded
-        ix->flow_ready = false;
-        ix->target_ready = false;
+        if (reset_flow) {  // the loop starts from an empty flow table
+            ix->flow_ready = false;
+            ix->target_ready = false;
+        }
         Events<2> ev(g);
         HIP_CHECK(hipEventRecord(ev.e[0], s));
         upload_capacity(ix, capacity);
@@ -375,6 +362,8 @@ void loading_round(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_b
         HIP_CHECK(hipStreamSynchronize(s));
         HIP_CHECK(hipEventElapsedTime(&cap_ms, ev.e[0], ev.e[1]));
     }
+    // sptt over the search's cost / finished (sorted order; the demand as
+    // search_loads uploaded it, read through qperm)
     HIP_CHECK(hipMemsetAsync(ix->vdf_acc.p, 0, 3 * sizeof(unsigned long long), s));
     (void)hipGetLastError();
     launch_sptt_reduce(ix->cost.p, ix->fin.p, ix->qperm.p, demand && nq ? ix->ld_demand.p : nullptr,
@@ -382,6 +371,116 @@ void loading_round(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_b
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(h, ix->vdf_acc.p, sizeof h, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// A caller's record is the leading fields of cpd_assign_conj_iter, which the
+// loop fills: cpd_assign_iter, then cpd_assign_line_iter's tail, then its own.
+#define SAME_PLACE(A, field) \
+    static_assert(offsetof(A, field) == offsetof(cpd_assign_conj_iter, field), #A "." #field)
+#define SAME_PLACES(A)                                                                   \
+    SAME_PLACE(A, finished); SAME_PLACE(A, sptt_lo); SAME_PLACE(A, sptt_hi);             \
+    SAME_PLACE(A, tstt_lo); SAME_PLACE(A, tstt_hi); SAME_PLACE(A, moves);                \
+    SAME_PLACE(A, changed); SAME_PLACE(A, search_ms); SAME_PLACE(A, loads_ms);           \
+    SAME_PLACE(A, vdf_ms)
+SAME_PLACES(cpd_assign_iter);
+SAME_PLACES(cpd_assign_line_iter);
+SAME_PLACE(cpd_assign_line_iter, lambda_q16);
+SAME_PLACE(cpd_assign_line_iter, evals);
+SAME_PLACE(cpd_assign_line_iter, g0_lo);
+SAME_PLACE(cpd_assign_line_iter, g0_hi);
+SAME_PLACE(cpd_assign_line_iter, xw0_lo);
+SAME_PLACE(cpd_assign_line_iter, xw0_hi);
+SAME_PLACE(cpd_assign_line_iter, line_ms);
+#undef SAME_PLACES
+#undef SAME_PLACE
+static_assert(sizeof(cpd_assign_iter) == offsetof(cpd_assign_conj_iter, lambda_q16) &&
+                  sizeof(cpd_assign_line_iter) == offsetof(cpd_assign_conj_iter, alpha_q16),
+              "a shorter record ends where the next one's own fields begin");
+
+// cpd_query_assign, _assign_line and _assign_conj.  Every iteration: a loading
+// and sptt (loading_round), then the rule's update — MSA turns the summed
+// table over k into weights (apply_vdf; no flow state, no early stop, its
+// errors not wrapped), the other two take a line-search step, plain or
+// conjugate (flow_step).  done: null for MSA, which always makes `iters`.
+template <class Rec>
+void assign_loop(Rule rule, cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                 const uint32_t* demand, const uint32_t* capacity, const cpd_vdf* f, uint32_t iters,
+                 Rec* out, uint32_t* done) {
+    static_assert(sizeof(Rec) <= sizeof(cpd_assign_conj_iter), "not a loop record");
+    const char* who = kLoopName[(int)rule];
+    const bool msa = rule == Rule::msa;
+    CPD_REQUIRE(ix && out && (done || msa), CPD_E_ARG, std::string(who) + ": null argument");
+    check_iters(iters, who);
+    check_vdf(f, false, who);
+    check_complete(ix, who);
+    check_capacity(ix, capacity, who);
+    for (uint32_t k = 0; k < iters; ++k) out[k] = Rec{};
+    if (done) *done = 0;
+    ix->g->select();
+    const uint32_t nq = ix->nq;
+    float cap_ms = 0.f;    // the capacity upload, in record 1
+    bool restart = false;  // the last conjugate direction went nowhere
+    for (uint32_t k = 1; k <= iters; ++k) {
+        cpd_search_stats ss{};
+        cpd_search_loads_info li{};
+        unsigned long long h[3] = {0, 0, 0};
+        loading_round(ix, opts, prefix_bytes, demand, capacity, rule, k, iters,
+                      msa && k > 1 ? CPD_LOADS_ACCUMULATE : 0u, !msa, ss, li, h, cap_ms);
+        cpd_assign_conj_iter r{};
+        if (msa) {
+            cpd_vdf fk = *f;
+            fk.load_div = k;
+            cpd_vdf_info vi{};
+            apply_vdf(ix, fk, &vi);
+            r.tstt_lo = vi.tstt_lo;
+            r.tstt_hi = vi.tstt_hi;
+            r.changed = vi.changed;
+            r.vdf_ms = vi.vdf_ms;
+        } else {
+            cpd_conj_info ci{};
+            try {
+                flow_step(ix, *f, rule == Rule::conj, restart ? 0u : CPD_ALPHA_CONJ, CPD_STEP_LINE,
+                          &ci);
+            } catch (const Error& e) {
+                if (k == 1) throw;
+                throw iteration_failed(e.code, rule, k, iters, e.what());
+            }
+            r.tstt_lo = ci.tstt_lo;
+            r.tstt_hi = ci.tstt_hi;
+            r.changed = ci.changed;
+            r.vdf_ms = ci.apply_ms;
+            r.lambda_q16 = ci.lambda_q16;
+            r.evals = ci.evals;
+            r.g0_lo = ci.g0_lo;
+            r.g0_hi = ci.g0_hi;
+            r.xw0_lo = ci.xw0_lo;
+            r.xw0_hi = ci.xw0_hi;
+            r.line_ms = ci.conj_ms + ci.line_ms;
+            r.alpha_q16 = ci.alpha_q16;
+            r.n_lo = ci.n_lo;
+            r.n_hi = ci.n_hi;
+            r.m_lo = ci.m_lo;
+            r.m_hi = ci.m_hi;
+            r.gy_lo = ci.gy_lo;
+            r.gy_hi = ci.gy_hi;
+        }
+        r.finished = h[2];
+        r.sptt_lo = h[0];
+        r.sptt_hi = h[1];
+        r.moves = li.moves;
+        r.search_ms = ss.kernel_ms + ss.tables_ms;
+        r.loads_ms = li.loads_ms;
+        r.vdf_ms += k == 1 ? cap_ms : 0.f;
+        std::memcpy(&out[k - 1], &r, sizeof(Rec));
+        if (msa) continue;
+        *done = k;
+        // lambda = 0 on a plain direction (the line rule's alpha is always 0):
+        // the weights stay and the next search would repeat this one; on a
+        // conjugate direction the next iteration restarts with alpha = 0.  The
+        // empty batch has nothing to iterate.
+        if ((k >= 2u && r.lambda_q16 == 0u && r.alpha_q16 == 0u) || nq == 0u) break;
+        restart = r.lambda_q16 == 0u && r.alpha_q16 > 0u;
+    }
 }
 
 }  // namespace
@@ -393,9 +492,7 @@ int cpd_index_weights_from_loads(cpd_index* ix, const uint32_t* capacity, const 
     return guarded([&] {
         CPD_REQUIRE(ix, CPD_E_ARG, "weights from loads: null index");
         check_vdf(f, true, "weights from loads");
-        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
-                    "weights from loads: index incomplete (" + std::to_string(ix->added) + " of " +
-                        std::to_string(ix->nrows) + " rows appended)");
+        check_complete(ix, "weights from loads");
         CPD_REQUIRE(ix->loads_ready, CPD_E_ARG,
                     "weights from loads: no load table resident (cpd_query_loads, "
                     "cpd_query_timed or cpd_query_search_loads first)");
@@ -434,109 +531,37 @@ int cpd_query_assign(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix
                      const uint32_t* demand, const uint32_t* capacity, const cpd_vdf* f,
                      uint32_t iters, cpd_assign_iter* out) {
     return guarded([&] {
-        CPD_REQUIRE(ix && out, CPD_E_ARG, "assign: null argument");
-        CPD_REQUIRE(iters >= 1u && iters <= 65535u, CPD_E_ARG,
-                    "assign: " + std::to_string(iters) + " iterations, 1 to 65535");
-        check_vdf(f, false, "assign");
-        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
-                    "assign: index incomplete (" + std::to_string(ix->added) + " of " +
-                        std::to_string(ix->nrows) + " rows appended)");
-        check_capacity(ix, capacity, "assign");
-        for (uint32_t k = 0; k < iters; ++k) out[k] = cpd_assign_iter{};
-        cpd_graph* g = ix->g;
-        g->select();
-        hipStream_t s = g->stream;
-        const uint32_t nq = ix->nq;
-        bool cap_ready = false;  // uploaded once, after the first loading succeeded
-        float cap_ms = 0.f;
-        for (uint32_t k = 1; k <= iters; ++k) {
-            cpd_assign_iter& r = out[k - 1];
-            cpd_search_stats ss{};
-            cpd_search_loads_info li{};
-            const int rc = cpd_query_search_loads(ix, opts, prefix_bytes, demand,
-                                                  k == 1 ? 0u : CPD_LOADS_ACCUMULATE, &ss, &li);
-            if (rc != CPD_OK) {
-                const std::string why = cpd_last_error();
-                if (k == 1) throw Error(rc, why);  // nothing has changed
-                throw Error(rc, "assign: iteration " + std::to_string(k) + " of " +
-                                    std::to_string(iters) + " failed, the table and weights are "
-                                    "those of " + std::to_string(k - 1) + " iterations: " + why);
-            }
-            if (!cap_ready) {
-                Events<2> ev(g);
-                HIP_CHECK(hipEventRecord(ev.e[0], s));
-                upload_capacity(ix, capacity);
-                HIP_CHECK(hipEventRecord(ev.e[1], s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                HIP_CHECK(hipEventElapsedTime(&cap_ms, ev.e[0], ev.e[1]));
-                cap_ready = true;
-            }
-            // sptt over the search's cost / finished (sorted order; the demand
-            // as search_loads uploaded it, read through qperm)
-            HIP_CHECK(hipMemsetAsync(ix->vdf_acc.p, 0, 3 * sizeof(unsigned long long), s));
-            (void)hipGetLastError();
-            launch_sptt_reduce(ix->cost.p, ix->fin.p, ix->qperm.p,
-                               demand && nq ? ix->ld_demand.p : nullptr, nq, ix->vdf_acc.p, s);
-            HIP_CHECK(hipGetLastError());
-            unsigned long long h[3] = {0, 0, 0};
-            HIP_CHECK(hipMemcpyAsync(h, ix->vdf_acc.p, sizeof h, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            cpd_vdf fk = *f;
-            fk.load_div = k;
-            cpd_vdf_info vi{};
-            apply_vdf(ix, fk, &vi);
-            r.finished = h[2];
-            r.sptt_lo = h[0];
-            r.sptt_hi = h[1];
-            r.tstt_lo = vi.tstt_lo;
-            r.tstt_hi = vi.tstt_hi;
-            r.moves = li.moves;
-            r.changed = vi.changed;
-            r.search_ms = ss.kernel_ms + ss.tables_ms;
-            r.loads_ms = li.loads_ms;
-            r.vdf_ms = vi.vdf_ms + (k == 1 ? cap_ms : 0.f);
-        }
+        assign_loop(Rule::msa, ix, opts, prefix_bytes, demand, capacity, f, iters, out, nullptr);
     });
 }
 
 int cpd_index_flow_step(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f,
                         uint32_t lambda_q16, cpd_flow_info* info) {
     return guarded([&] {
-        CPD_REQUIRE(ix, CPD_E_ARG, "flow step: null index");
-        check_vdf(f, false, "flow step");
-        CPD_REQUIRE(lambda_q16 <= 65536u || lambda_q16 == CPD_STEP_LINE, CPD_E_ARG,
-                    "flow step: lambda_q16 " + std::to_string(lambda_q16) +
-                        " is neither 0..65536 nor CPD_STEP_LINE");
-        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
-                    "flow step: index incomplete (" + std::to_string(ix->added) + " of " +
-                        std::to_string(ix->nrows) + " rows appended)");
-        check_flow_table(ix, "flow step");
-        check_capacity(ix, capacity, "flow step");
-        ix->g->select();
-        upload_capacity(ix, capacity);
-        flow_step(ix, *f, lambda_q16, info);
+        cpd_conj_info ci{};
+        checked_step(ix, capacity, f, false, 0u, lambda_q16, &ci);
+        if (!info) return;
+        *info = cpd_flow_info{};
+        info->lambda_q16 = ci.lambda_q16;
+        info->evals = ci.evals;
+        info->g0_lo = ci.g0_lo;
+        info->g0_hi = ci.g0_hi;
+        info->xw0_lo = ci.xw0_lo;
+        info->xw0_hi = ci.xw0_hi;
+        info->tstt_lo = ci.tstt_lo;
+        info->tstt_hi = ci.tstt_hi;
+        info->changed = ci.changed;
+        info->line_ms = ci.line_ms;
+        info->apply_ms = ci.apply_ms;
     });
 }
 
 int cpd_index_flow_step_conj(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f,
                              uint32_t alpha_q16, uint32_t lambda_q16, cpd_conj_info* info) {
     return guarded([&] {
-        CPD_REQUIRE(ix, CPD_E_ARG, "conjugate step: null index");
-        check_vdf(f, false, "conjugate step");
-        CPD_REQUIRE(alpha_q16 <= CPD_ALPHA_MAX || alpha_q16 == CPD_ALPHA_CONJ, CPD_E_ARG,
-                    "conjugate step: alpha_q16 " + std::to_string(alpha_q16) +
-                        " is neither 0..64881 nor CPD_ALPHA_CONJ");
-        CPD_REQUIRE(lambda_q16 <= 65536u || lambda_q16 == CPD_STEP_LINE, CPD_E_ARG,
-                    "conjugate step: lambda_q16 " + std::to_string(lambda_q16) +
-                        " is neither 0..65536 nor CPD_STEP_LINE");
-        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
-                    "conjugate step: index incomplete (" + std::to_string(ix->added) + " of " +
-                        std::to_string(ix->nrows) + " rows appended)");
-        check_flow_table(ix, "conjugate step");
-        check_capacity(ix, capacity, "conjugate step");
-        ix->g->select();
-        upload_capacity(ix, capacity);
-        conj_step(ix, *f, alpha_q16, lambda_q16, info);
+        cpd_conj_info ci{};
+        checked_step(ix, capacity, f, true, alpha_q16, lambda_q16, &ci);
+        if (info) *info = ci;
     });
 }
 
@@ -545,7 +570,7 @@ int cpd_index_flow_fetch(cpd_index* ix, uint64_t* flow) {
         CPD_REQUIRE(ix, CPD_E_ARG, "flow fetch: null index");
         CPD_REQUIRE(ix->flow_ready, CPD_E_ARG,
                     "flow fetch: no flow table resident (cpd_index_flow_step first)");
-        fetch_slot_table(ix, ix->fl_tab.p, flow, "flow fetch");
+        fetch_slot_table(ix, ix->fl_tab.p, ix->fl_out, flow, "flow fetch");
     });
 }
 
@@ -554,7 +579,7 @@ int cpd_index_target_fetch(cpd_index* ix, uint64_t* s) {
         CPD_REQUIRE(ix, CPD_E_ARG, "target fetch: null index");
         CPD_REQUIRE(ix->flow_ready && ix->target_ready, CPD_E_ARG,
                     "target fetch: no target table resident (cpd_index_flow_step_conj first)");
-        fetch_slot_table(ix, ix->tg_tab.p, s, "target fetch");
+        fetch_slot_table(ix, ix->tg_tab.p, ix->fl_out, s, "target fetch");
     });
 }
 
@@ -574,58 +599,7 @@ int cpd_query_assign_line(cpd_index* ix, const cpd_search_opts* opts, uint64_t p
                           const uint32_t* demand, const uint32_t* capacity, const cpd_vdf* f,
                           uint32_t iters, cpd_assign_line_iter* out, uint32_t* done) {
     return guarded([&] {
-        CPD_REQUIRE(ix && out && done, CPD_E_ARG, "assign line: null argument");
-        CPD_REQUIRE(iters >= 1u && iters <= 65535u, CPD_E_ARG,
-                    "assign line: " + std::to_string(iters) + " iterations, 1 to 65535");
-        check_vdf(f, false, "assign line");
-        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
-                    "assign line: index incomplete (" + std::to_string(ix->added) + " of " +
-                        std::to_string(ix->nrows) + " rows appended)");
-        check_capacity(ix, capacity, "assign line");
-        for (uint32_t k = 0; k < iters; ++k) out[k] = cpd_assign_line_iter{};
-        *done = 0;
-        ix->g->select();
-        const uint32_t nq = ix->nq;
-        float cap_ms = 0.f;
-        for (uint32_t k = 1; k <= iters; ++k) {
-            cpd_assign_line_iter& r = out[k - 1];
-            cpd_search_stats ss{};
-            cpd_search_loads_info li{};
-            unsigned long long h[3] = {0, 0, 0};
-            loading_round(ix, opts, prefix_bytes, demand, capacity, k, iters, "assign line", ss, li,
-                          h, cap_ms);
-            cpd_flow_info fi{};
-            try {
-                flow_step(ix, *f, CPD_STEP_LINE, &fi);
-            } catch (const Error& e) {
-                if (k == 1) throw;
-                throw Error(e.code, "assign line: iteration " + std::to_string(k) + " of " +
-                                        std::to_string(iters) + " failed, the flow table and "
-                                        "weights are those of " + std::to_string(k - 1) +
-                                        " iterations: " + e.what());
-            }
-            r.finished = h[2];
-            r.sptt_lo = h[0];
-            r.sptt_hi = h[1];
-            r.tstt_lo = fi.tstt_lo;
-            r.tstt_hi = fi.tstt_hi;
-            r.moves = li.moves;
-            r.changed = fi.changed;
-            r.search_ms = ss.kernel_ms + ss.tables_ms;
-            r.loads_ms = li.loads_ms;
-            r.vdf_ms = fi.apply_ms + (k == 1 ? cap_ms : 0.f);
-            r.lambda_q16 = fi.lambda_q16;
-            r.evals = fi.evals;
-            r.g0_lo = fi.g0_lo;
-            r.g0_hi = fi.g0_hi;
-            r.xw0_lo = fi.xw0_lo;
-            r.xw0_hi = fi.xw0_hi;
-            r.line_ms = fi.line_ms;
-            *done = k;
-            // lambda = 0: the weights stay, the next search would repeat this
-            // one; the empty batch has nothing to iterate
-            if ((k >= 2u && fi.lambda_q16 == 0u) || nq == 0u) break;
-        }
+        assign_loop(Rule::line, ix, opts, prefix_bytes, demand, capacity, f, iters, out, done);
     });
 }
 
@@ -633,69 +607,7 @@ int cpd_query_assign_conj(cpd_index* ix, const cpd_search_opts* opts, uint64_t p
                           const uint32_t* demand, const uint32_t* capacity, const cpd_vdf* f,
                           uint32_t iters, cpd_assign_conj_iter* out, uint32_t* done) {
     return guarded([&] {
-        CPD_REQUIRE(ix && out && done, CPD_E_ARG, "assign conj: null argument");
-        CPD_REQUIRE(iters >= 1u && iters <= 65535u, CPD_E_ARG,
-                    "assign conj: " + std::to_string(iters) + " iterations, 1 to 65535");
-        check_vdf(f, false, "assign conj");
-        CPD_REQUIRE(ix->added == ix->nrows, CPD_E_ARG,
-                    "assign conj: index incomplete (" + std::to_string(ix->added) + " of " +
-                        std::to_string(ix->nrows) + " rows appended)");
-        check_capacity(ix, capacity, "assign conj");
-        for (uint32_t k = 0; k < iters; ++k) out[k] = cpd_assign_conj_iter{};
-        *done = 0;
-        ix->g->select();
-        const uint32_t nq = ix->nq;
-        float cap_ms = 0.f;
-        bool restart = false;  // the last conjugate direction went nowhere
-        for (uint32_t k = 1; k <= iters; ++k) {
-            cpd_assign_conj_iter& r = out[k - 1];
-            cpd_search_stats ss{};
-            cpd_search_loads_info li{};
-            unsigned long long h[3] = {0, 0, 0};
-            loading_round(ix, opts, prefix_bytes, demand, capacity, k, iters, "assign conj", ss, li,
-                          h, cap_ms);
-            cpd_conj_info ci{};
-            try {
-                conj_step(ix, *f, restart ? 0u : CPD_ALPHA_CONJ, CPD_STEP_LINE, &ci);
-            } catch (const Error& e) {
-                if (k == 1) throw;
-                throw Error(e.code, "assign conj: iteration " + std::to_string(k) + " of " +
-                                        std::to_string(iters) + " failed, the flow table and "
-                                        "weights are those of " + std::to_string(k - 1) +
-                                        " iterations: " + e.what());
-            }
-            r.finished = h[2];
-            r.sptt_lo = h[0];
-            r.sptt_hi = h[1];
-            r.tstt_lo = ci.tstt_lo;
-            r.tstt_hi = ci.tstt_hi;
-            r.moves = li.moves;
-            r.changed = ci.changed;
-            r.search_ms = ss.kernel_ms + ss.tables_ms;
-            r.loads_ms = li.loads_ms;
-            r.vdf_ms = ci.apply_ms + (k == 1 ? cap_ms : 0.f);
-            r.lambda_q16 = ci.lambda_q16;
-            r.evals = ci.evals;
-            r.g0_lo = ci.g0_lo;
-            r.g0_hi = ci.g0_hi;
-            r.xw0_lo = ci.xw0_lo;
-            r.xw0_hi = ci.xw0_hi;
-            r.line_ms = ci.conj_ms + ci.line_ms;
-            r.alpha_q16 = ci.alpha_q16;
-            r.n_lo = ci.n_lo;
-            r.n_hi = ci.n_hi;
-            r.m_lo = ci.m_lo;
-            r.m_hi = ci.m_hi;
-            r.gy_lo = ci.gy_lo;
-            r.gy_hi = ci.gy_hi;
-            *done = k;
-            // lambda = 0 on a plain direction: the weights stay and the next
-            // search would repeat this one; on a conjugate direction the next
-            // iteration restarts with alpha = 0.  The empty batch has nothing
-            // to iterate.
-            if ((k >= 2u && ci.lambda_q16 == 0u && ci.alpha_q16 == 0u) || nq == 0u) break;
-            restart = ci.lambda_q16 == 0u && ci.alpha_q16 > 0u;
-        }
+        assign_loop(Rule::conj, ix, opts, prefix_bytes, demand, capacity, f, iters, out, done);
     });
 }
 

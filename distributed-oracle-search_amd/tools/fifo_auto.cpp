@@ -337,6 +337,47 @@ static void write_assign(cpd_index* ix, const std::string& qfile, const cpd::io:
     }
 }
 
+// What follows the common fields on an .assign line: the rule's step and gap terms.
+static std::string assign_tail(const cpd_assign_iter&) { return ""; }
+static std::string assign_tail(const cpd_assign_line_iter& r) {
+    return " " + std::to_string(r.lambda_q16) + " " + dec128_signed(r.g0_lo, r.g0_hi) + " " +
+           dec128(r.xw0_lo, r.xw0_hi);
+}
+static std::string assign_tail(const cpd_assign_conj_iter& r) {
+    return " " + std::to_string(r.lambda_q16) + " " + dec128_signed(r.gy_lo, r.gy_hi) + " " +
+           dec128(r.xw0_lo, r.xw0_hi) + " " + std::to_string(r.alpha_q16);
+}
+
+// cpd_query_assign in the other two loops' shape: it makes every record.
+static int assign_msa(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                      const uint32_t* demand, const uint32_t* capacity, const cpd_vdf* f,
+                      uint32_t iters, cpd_assign_iter* out, uint32_t* done) {
+    *done = iters;
+    return cpd_query_assign(ix, opts, prefix_bytes, demand, capacity, f, iters, out);
+}
+
+// An --assign request through one of the three loops (demand 1 per query):
+// the text of one .assign line per record made; returns their summed search_ms.
+template <class Rec>
+static double run_assign(int (*loop)(cpd_index*, const cpd_search_opts*, uint64_t, const uint32_t*,
+                                     const uint32_t*, const cpd_vdf*, uint32_t, Rec*, uint32_t*),
+                         cpd_index* ix, const cpd_search_opts& so, const std::vector<uint32_t>& cap,
+                         const cpd_vdf& vdf, uint32_t iters, std::vector<std::string>& lines) {
+    std::vector<Rec> it(iters);
+    uint32_t made = 0;
+    if (loop(ix, &so, 0, nullptr, cap.data(), &vdf, iters, it.data(), &made) != CPD_OK)
+        throw std::runtime_error(cpd_last_error());
+    double search_ms = 0.0;
+    for (uint32_t k = 0; k < made; ++k) {
+        const Rec& r = it[k];
+        lines.push_back(std::to_string(r.finished) + " " + dec128(r.sptt_lo, r.sptt_hi) + " " +
+                        dec128(r.tstt_lo, r.tstt_hi) + " " + std::to_string(r.moves) + " " +
+                        std::to_string(r.changed) + assign_tail(r));
+        search_ms += r.search_ms;
+    }
+    return search_ms;
+}
+
 // <query file>.dep of a --timed request: one unsigned integer per query line;
 // no such file: every query leaves at 0 (dep stays empty)
 static void read_departures(const std::string& qfile, size_t nq, std::vector<uint64_t>& dep) {
@@ -913,60 +954,16 @@ int main(int argc, char** argv) {
                 active_diff.clear();
                 static std::vector<uint32_t> cap;
                 cap.assign(g.m, (uint32_t)assign_cap);
-                // one record per iteration: what both loops report, then the
-                // line rule's step and gap terms
-                auto common = [](uint64_t finished, uint64_t sl, uint64_t sh, uint64_t tl, uint64_t th,
-                                 uint64_t moves, uint64_t changed) {
-                    return std::to_string(finished) + " " + dec128(sl, sh) + " " + dec128(tl, th) +
-                           " " + std::to_string(moves) + " " + std::to_string(changed);
-                };
+                const uint32_t iters = (uint32_t)assign_iters;
                 std::vector<std::string> lines;
-                double search_ms = 0.0;
-                if (step_line) {
-                    std::vector<cpd_assign_line_iter> it((size_t)assign_iters);
-                    uint32_t made = 0;
-                    rc = cpd_query_assign_line(ix, &so, 0, nullptr, cap.data(), &vdf,
-                                               (uint32_t)assign_iters, it.data(), &made);
-                    if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                    for (uint32_t k = 0; k < made; ++k) {
-                        const cpd_assign_line_iter& r = it[k];
-                        lines.push_back(common(r.finished, r.sptt_lo, r.sptt_hi, r.tstt_lo, r.tstt_hi,
-                                               r.moves, r.changed) +
-                                        " " + std::to_string(r.lambda_q16) + " " +
-                                        dec128_signed(r.g0_lo, r.g0_hi) + " " +
-                                        dec128(r.xw0_lo, r.xw0_hi));
-                        search_ms += r.search_ms;
-                    }
-                    write_flow(ix, qfile, g);
-                } else if (step_conj) {
-                    std::vector<cpd_assign_conj_iter> it((size_t)assign_iters);
-                    uint32_t made = 0;
-                    rc = cpd_query_assign_conj(ix, &so, 0, nullptr, cap.data(), &vdf,
-                                               (uint32_t)assign_iters, it.data(), &made);
-                    if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                    for (uint32_t k = 0; k < made; ++k) {
-                        const cpd_assign_conj_iter& r = it[k];
-                        lines.push_back(common(r.finished, r.sptt_lo, r.sptt_hi, r.tstt_lo, r.tstt_hi,
-                                               r.moves, r.changed) +
-                                        " " + std::to_string(r.lambda_q16) + " " +
-                                        dec128_signed(r.gy_lo, r.gy_hi) + " " +
-                                        dec128(r.xw0_lo, r.xw0_hi) + " " +
-                                        std::to_string(r.alpha_q16));
-                        search_ms += r.search_ms;
-                    }
-                    write_flow(ix, qfile, g);
-                } else {
-                    std::vector<cpd_assign_iter> it((size_t)assign_iters);
-                    rc = cpd_query_assign(ix, &so, 0, nullptr, cap.data(), &vdf,
-                                          (uint32_t)assign_iters, it.data());
-                    if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                    for (const cpd_assign_iter& r : it) {
-                        lines.push_back(common(r.finished, r.sptt_lo, r.sptt_hi, r.tstt_lo, r.tstt_hi,
-                                               r.moves, r.changed));
-                        search_ms += r.search_ms;
-                    }
-                    write_loads(ix, qfile, g, 1);
-                }
+                const double search_ms =
+                    step_line   ? run_assign<cpd_assign_line_iter>(cpd_query_assign_line, ix, so, cap,
+                                                                   vdf, iters, lines)
+                    : step_conj ? run_assign<cpd_assign_conj_iter>(cpd_query_assign_conj, ix, so, cap,
+                                                                   vdf, iters, lines)
+                                : run_assign<cpd_assign_iter>(assign_msa, ix, so, cap, vdf, iters, lines);
+                if (step_line || step_conj) write_flow(ix, qfile, g);
+                else write_loads(ix, qfile, g, 1);
                 write_assign(ix, qfile, g, lines);
                 // the answer line's sums, from the last iteration's search
                 std::vector<uint32_t> cnt(5 * nq), plen(nq);

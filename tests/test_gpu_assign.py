@@ -308,12 +308,15 @@ def test_assign_variants(loop):
     ix.set_weights(None)
     recs = ix.assign(loop.s, loop.t, loop.capacity, 1, loop.demand)
     check_assign(ix, recs, loop_want(iters=1), "one iteration")
+    ix.flow_step(loop.capacity)  # a flow table: MSA keeps none and leaves this one alone
+    flow = ix.flow_fetch()
     # a warm start: iteration 1 searches under the weights the index holds
     wc = cpd.synth_congestion(loop.g.w, frac=0.2, lo=1.0, hi=3.0, seed=4)
     ix.set_weights(wc)
     recs = ix.assign(loop.s, loop.t, loop.capacity, 3, loop.demand)
     want = loop_want(warm=wc, iters=3)
     check_assign(ix, recs, want, "warm start")
+    np.testing.assert_array_equal(ix.flow_fetch(), flow)
     assert want[0][0]["sptt"] != loop_want(iters=1)[0][0]["sptt"]
     # the empty batch: all-zero records, a zeroed table, w0 on every edge
     none = np.zeros(0, np.uint32)
