@@ -26,7 +26,7 @@ LDLIBS    := -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib
 
 HOST_OBJS := $(BLD)/host_util.o $(BLD)/ch.o $(BLD)/ch_gpu.o $(BLD)/plan.o $(BLD)/cpd_io.o \
              $(BLD)/cpd_switches.o $(BLD)/cpd_device.o $(BLD)/cpd_graph.o $(BLD)/cpd_rows.o \
-             $(BLD)/cpd_index.o $(BLD)/cpd_search.o $(BLD)/cpd_assign.o
+             $(BLD)/cpd_index.o $(BLD)/cpd_query.o $(BLD)/cpd_search.o $(BLD)/cpd_assign.o
 DEV_OBJS  := $(BLD)/cpd_kernels.o $(BLD)/ch_kernels.o $(BLD)/assign_kernels.o
 TOOLS     := make_cpd_auto fifo_auto gen_distribute_conf gen_synth
 BINS      := $(addprefix bin/,$(TOOLS))

@@ -1,5 +1,5 @@
 // Private to the GPU half of the C ABI (cpd_device / cpd_graph / cpd_rows /
-// cpd_index / cpd_search .cpp): device plumbing and the three objects behind
+// cpd_index / cpd_query / cpd_search .cpp): device plumbing and the three objects behind
 // the opaque handles of cpd_api.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -460,6 +460,8 @@ struct cpd_index {
         // B per row)
         return nrows > 0 && 4.0 * (double)declared > 4.0 * (double)g->wpr() * nrows;
     }
+    // the adjacency a walk that costs its moves reads: the custom weights' when set
+    const uint32_t* walk_adj() const { return custom_w ? adj_sel.p : g->adj.p; }
     // CPD-search: per-row tables when they fit (hrow free-flow heuristic,
     // crow / lrow incumbent cost and moves under the current weights; rebuilt
     // for new weights), row target columns, workspace (per lane slot),
@@ -606,4 +608,14 @@ void ensure_dense(cpd_index* ix);           // cpd_index.cpp
 void reset_load_table(cpd_index* ix, uint32_t planes, uint32_t slice_moves,
                       uint64_t period);     // cpd_index.cpp
 void ensure_slot_of_edge(cpd_graph* g);     // cpd_index.cpp
+// cpd_query.cpp: checks and the paths tail its calls share with cpd_search.cpp's.
+// `who` is the call's message prefix ("loads", "search paths", ...).
+void require_complete(const cpd_index* ix, const char* who);  // every declared row appended
+void require_load_slots(const cpd_graph* g, const char* who);  // adjacency slots fit the load kernels' u32
+// The tail of cpd_query_paths / _search_paths: the empty batch's return; the
+// offsets (ix->poff) copied to poff_h and pnodes carved for their total, which
+// is returned; poff_h copied out and paths_ready set.
+void paths_empty(cpd_index* ix, uint64_t* offsets);
+uint64_t paths_reserve(cpd_index* ix, const char* who);
+void paths_copy_out(cpd_index* ix, uint64_t* offsets);
 }  // namespace cpd

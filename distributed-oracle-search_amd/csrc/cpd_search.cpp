@@ -473,7 +473,7 @@ uint64_t run_search(cpd_index* ix, const cpd_search_opts* opts, cpd_search_stats
     g->select();
     const uint32_t nq = ix->nq;
     if (!ix->dense_ready) ensure_dense(ix);
-    const uint32_t* adj_w = ix->custom_w ? ix->adj_sel.p : g->adj.p;
+    const uint32_t* adj_w = ix->walk_adj();
     const bool tables = decide_tables(ix, o);
     const double tables_ms = build_search_tables(ix, adj_w, tables);
     uint64_t pool_entries = 0;
@@ -522,6 +522,15 @@ struct PathsScratch {
     }
 };
 
+// Every prefix of a PATHS call must have been stored: `used` nodes in a pool
+// of pool_bytes.
+void require_prefix_pool(const char* who, uint64_t used, uint64_t pool_bytes) {
+    CPD_REQUIRE(used <= pool_bytes / 4u, CPD_E_OOM,
+                std::string(who) + ": the prefixes need " + std::to_string(4ull * used) +
+                    " bytes of prefix pool, " + std::to_string(pool_bytes) +
+                    " were given: call again with prefix_bytes >= " + std::to_string(4ull * used));
+}
+
 }  // namespace
 
 extern "C" {
@@ -550,15 +559,9 @@ int cpd_query_search_paths(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
         }
         // the search's results are whole and fetchable from here on, whatever
         // becomes of the paths
-        CPD_REQUIRE(used <= pool_bytes / 4u, CPD_E_OOM,
-                    "search paths: the prefixes need " + std::to_string(4ull * used) +
-                        " bytes of prefix pool, " + std::to_string(pool_bytes) +
-                        " were given: call again with prefix_bytes >= " +
-                        std::to_string(4ull * used));
+        require_prefix_pool("search paths", used, pool_bytes);
         if (!nq) {
-            offsets[0] = 0;
-            ix->poff_h.assign(1, 0);
-            ix->paths_ready = true;
+            paths_empty(ix, offsets);
             return;
         }
         cpd_graph* g = ix->g;
@@ -579,22 +582,7 @@ int cpd_query_search_paths(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
                                              ix->poff.p, s));
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(ev.e[1], s));
-        ix->poff_h.resize((size_t)nq + 1u);
-        HIP_CHECK(hipMemcpyAsync(ix->poff_h.data(), ix->poff.p, ((size_t)nq + 1u) * sizeof(uint64_t),
-                                 hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        const uint64_t total = ix->poff_h[nq];
-        try {  // the index's path buffer (cpd_query_paths: from the arena when there is one)
-            ArenaScope carve;
-            ix->pnodes.alloc((size_t)total);
-        } catch (const Error& e) {
-            (void)hipGetLastError();
-            if (e.code != CPD_E_OOM) throw;
-            throw Error(CPD_E_OOM, "search paths: " + std::to_string(4ull * total) +
-                                       " bytes of HBM for " + std::to_string(total) +
-                                       " path nodes of " + std::to_string(nq) +
-                                       " queries do not fit");
-        }
+        const uint64_t total = paths_reserve(ix, "search paths");  // the index's path buffer
         // the suffixes: the table-search walk from every v* (k_moves < 0: to
         // t) into the end of its path — over the dense rows the search
         // itself used, with buffers of its own (the search's cost / hops /
@@ -624,8 +612,7 @@ int cpd_query_search_paths(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
             info->nodes = total;
             info->paths_ms = (double)ms_off + (double)ms_fill;
         }
-        std::memcpy(offsets, ix->poff_h.data(), ((size_t)nq + 1u) * sizeof(uint64_t));
-        ix->paths_ready = true;
+        paths_copy_out(ix, offsets);
     });
 }
 
@@ -646,9 +633,7 @@ int cpd_query_search_loads(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
                         " slices of " + std::to_string(ix->ld_slice_moves) +
                         " moves: a search loads one plane");
         cpd_graph* g = ix->g;
-        // the kernels keep a slot as u32, 0xFFFFFFFF = none
-        CPD_REQUIRE(((uint64_t)g->n << g->adj_shift) < 0xFFFFFFFFull, CPD_E_RANGE,
-                    "search loads: 2^32 adjacency slots or more");
+        require_load_slots(g, "search loads");
         const uint32_t nq = ix->nq;
         ix->paths_ready = false;
         PathsScratch scratch{ix};
@@ -660,11 +645,7 @@ int cpd_query_search_loads(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
         }
         // the search's results are whole and fetchable from here on; the load
         // table is touched only once every prefix is known to be stored
-        CPD_REQUIRE(used <= pool_bytes / 4u, CPD_E_OOM,
-                    "search loads: the prefixes need " + std::to_string(4ull * used) +
-                        " bytes of prefix pool, " + std::to_string(pool_bytes) +
-                        " were given: call again with prefix_bytes >= " +
-                        std::to_string(4ull * used));
+        require_prefix_pool("search loads", used, pool_bytes);
         if (!keep) reset_load_table(ix, 1, 0, 0);
         if (!nq) return;
         hipStream_t s = g->stream;
@@ -682,7 +663,7 @@ int cpd_query_search_loads(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
         w_fin.alloc(nq);
         cnt.alloc(5);
         HIP_CHECK(hipMemsetAsync(cnt.p, 0, 5 * sizeof(unsigned long long), s));
-        const uint32_t* adj_w = ix->custom_w ? ix->adj_sel.p : g->adj.p;
+        const uint32_t* adj_w = ix->walk_adj();
         Events<2> ev(g);
         HIP_CHECK(hipEventRecord(ev.e[0], s));
         (void)hipGetLastError();
