@@ -75,7 +75,7 @@ $(BLD)/assign_kernels.o: $(SRC)/assign_kernels.hip $(SRC)/assign_kernels.hpp inc
 $(LIB): $(HOST_OBJS) $(DEV_OBJS)
 	$(CXX) -shared -fopenmp -o $@ $^ $(LDLIBS)
 
-bin/%: $(PKG)/tools/%.cpp $(LIB) $(HDRS) | $(BLD)
+bin/%: $(PKG)/tools/%.cpp $(LIB) $(HDRS) $(wildcard $(PKG)/tools/*.hpp) | $(BLD)
 	$(CXX) $(CXXFLAGS) -o $@ $< -L$(PKG) -lcpd -Wl,-rpath,'$$ORIGIN/../$(PKG)' $(LDLIBS)
 
 $(ORACLE): oracle/cpd_oracle.c

@@ -121,6 +121,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -175,6 +176,37 @@ static std::string read_all(const std::string& path) {
     return s;
 }
 
+// A library call of a request that failed: the request fails (cli::check exits).
+static void must(int rc) {
+    if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
+}
+
+// A side file of a request, written as <path>.tmp and renamed into place by
+// commit(ok: every write succeeded); left any other way, the temporary is
+// closed and unlinked.
+struct SideFile {
+    const std::string path, tmp;
+    std::FILE* f;
+    explicit SideFile(const std::string& p) : path(p), tmp(p + ".tmp"), f(std::fopen(tmp.c_str(), "w")) {
+        if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    }
+    SideFile(const SideFile&) = delete;
+    ~SideFile() {
+        if (f) std::fclose(f), ::unlink(tmp.c_str());
+    }
+    void commit(bool ok) {
+        ok = std::fclose(f) == 0 && ok;
+        f = nullptr;
+        place(ok, tmp, path);
+    }
+    // The tail alone, for a temporary somebody else wrote.
+    static void place(bool ok, const std::string& tmp, const std::string& path) {
+        if (ok && ::rename(tmp.c_str(), path.c_str()) == 0) return;
+        ::unlink(tmp.c_str());
+        throw std::runtime_error("cannot write " + path);
+    }
+};
+
 // <query file>.paths: the walks' nodes, fetched and written in pieces of at
 // most ~64M nodes (host memory stays bounded however long the paths are)
 static void write_paths(cpd_index* ix, const std::string& qfile, const std::vector<uint32_t>& s,
@@ -182,11 +214,9 @@ static void write_paths(cpd_index* ix, const std::string& qfile, const std::vect
     constexpr uint64_t kPiece = 64ull << 20;
     const size_t nq = s.size();
     std::vector<uint8_t> fin(nq);
-    if (cpd_query_fetch(ix, nullptr, nullptr, fin.data()) != CPD_OK)
-        throw std::runtime_error(cpd_last_error());
-    const std::string path = qfile + ".paths", tmp = path + ".tmp";
-    std::FILE* f = std::fopen(tmp.c_str(), "w");
-    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    must(cpd_query_fetch(ix, nullptr, nullptr, fin.data()));
+    SideFile side(qfile + ".paths");
+    std::FILE* f = side.f;
     std::vector<uint32_t> nodes;
     std::string out;
     auto put = [&out](uint64_t v, char sep) {
@@ -201,11 +231,7 @@ static void write_paths(cpd_index* ix, const std::string& qfile, const std::vect
         size_t q1 = q0 + 1;
         while (q1 < nq && off[q1 + 1] - off[q0] <= kPiece) ++q1;
         nodes.resize((size_t)(off[q1] - off[q0]));
-        if (cpd_query_paths_fetch(ix, (uint32_t)q0, (uint32_t)(q1 - q0), nodes.data()) != CPD_OK) {
-            std::fclose(f);
-            ::unlink(tmp.c_str());
-            throw std::runtime_error(cpd_last_error());
-        }
+        must(cpd_query_paths_fetch(ix, (uint32_t)q0, (uint32_t)(q1 - q0), nodes.data()));
         for (size_t q = q0; q < q1; ++q) {
             const uint64_t len = off[q + 1] - off[q];
             put(s[q], ' ');
@@ -222,11 +248,7 @@ static void write_paths(cpd_index* ix, const std::string& qfile, const std::vect
         q0 = q1;
     }
     if (ok && !out.empty()) ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
-    ok = std::fclose(f) == 0 && ok;
-    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
-        ::unlink(tmp.c_str());
-        throw std::runtime_error("cannot write " + path);
-    }
+    side.commit(ok);
 }
 
 // <query file>.res of a --costs request: s t moves finished cost_0 ... per query
@@ -236,11 +258,9 @@ static void write_costs(cpd_index* ix, const std::string& qfile, const std::vect
     std::vector<uint64_t> costs(nq * cols);
     std::vector<uint32_t> hops(nq);
     std::vector<uint8_t> fin(nq);
-    if (cpd_query_costs_fetch(ix, costs.data(), hops.data(), fin.data()) != CPD_OK)
-        throw std::runtime_error(cpd_last_error());
-    const std::string path = qfile + ".res", tmp = path + ".tmp";
-    std::FILE* f = std::fopen(tmp.c_str(), "w");
-    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    must(cpd_query_costs_fetch(ix, costs.data(), hops.data(), fin.data()));
+    SideFile side(qfile + ".res");
+    std::FILE* f = side.f;
     bool ok = true;
     for (size_t q = 0; q < nq && ok; ++q) {
         ok = std::fprintf(f, "%u %u %u %u", s[q], t[q], hops[q], fin[q] == 1 ? 1u : 0u) > 0;
@@ -248,19 +268,14 @@ static void write_costs(cpd_index* ix, const std::string& qfile, const std::vect
             ok = std::fprintf(f, " %llu", (unsigned long long)costs[q * cols + j]) > 0;
         ok = ok && std::fputc('\n', f) != EOF;
     }
-    ok = std::fclose(f) == 0 && ok;
-    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
-        ::unlink(tmp.c_str());
-        throw std::runtime_error("cannot write " + path);
-    }
+    side.commit(ok);
 }
 
 // <query file>.loads: edge from to load_0 ... per edge with any non-zero value
 static void write_load_values(const std::string& qfile, const cpd::io::XYGraph& g, size_t slices,
                               const std::vector<uint64_t>& loads) {
-    const std::string path = qfile + ".loads", tmp = path + ".tmp";
-    std::FILE* f = std::fopen(tmp.c_str(), "w");
-    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    SideFile side(qfile + ".loads");
+    std::FILE* f = side.f;
     bool ok = true;
     for (uint32_t a = 0; a < g.n && ok; ++a)
         for (uint32_t e = g.row_ptr[a]; e < g.row_ptr[a + 1] && ok; ++e) {
@@ -272,26 +287,21 @@ static void write_load_values(const std::string& qfile, const cpd::io::XYGraph& 
                 ok = std::fprintf(f, " %llu", (unsigned long long)loads[j * g.m + e]) > 0;
             ok = ok && std::fputc('\n', f) != EOF;
         }
-    ok = std::fclose(f) == 0 && ok;
-    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
-        ::unlink(tmp.c_str());
-        throw std::runtime_error("cannot write " + path);
-    }
+    side.commit(ok);
 }
 
 // <query file>.loads of a --loads request: the resident table
 static void write_loads(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g,
                         size_t slices) {
     std::vector<uint64_t> loads(slices * g.m);
-    if (cpd_query_loads_fetch(ix, loads.data()) != CPD_OK)
-        throw std::runtime_error(cpd_last_error());
+    must(cpd_query_loads_fetch(ix, loads.data()));
     write_load_values(qfile, g, slices, loads);
 }
 
 // <query file>.loads of an --assign --step line request: the flow's volumes
 static void write_flow(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g) {
     std::vector<uint64_t> x(g.m);
-    if (cpd_index_flow_fetch(ix, x.data()) != CPD_OK) throw std::runtime_error(cpd_last_error());
+    must(cpd_index_flow_fetch(ix, x.data()));
     for (uint64_t& v : x) v >>= 16;
     write_load_values(qfile, g, 1, x);
 }
@@ -315,26 +325,18 @@ static std::string dec128_signed(uint64_t lo, uint64_t hi) {
 // of text per iteration, then the final weights
 static void write_assign(cpd_index* ix, const std::string& qfile, const cpd::io::XYGraph& g,
                          const std::vector<std::string>& lines) {
-    std::string path = qfile + ".assign", tmp = path + ".tmp";
-    std::FILE* f = std::fopen(tmp.c_str(), "w");
-    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
-    bool ok = true;
-    for (size_t k = 0; k < lines.size() && ok; ++k)
-        ok = std::fprintf(f, "%zu %s\n", k + 1, lines[k].c_str()) > 0;
-    ok = std::fclose(f) == 0 && ok;
-    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
-        ::unlink(tmp.c_str());
-        throw std::runtime_error("cannot write " + path);
+    {
+        SideFile side(qfile + ".assign");
+        bool ok = true;
+        for (size_t k = 0; k < lines.size() && ok; ++k)
+            ok = std::fprintf(side.f, "%zu %s\n", k + 1, lines[k].c_str()) > 0;
+        side.commit(ok);
     }
     std::vector<uint32_t> w(g.m);
-    if (cpd_index_get_weights(ix, w.data()) != CPD_OK) throw std::runtime_error(cpd_last_error());
-    path = qfile + ".diff";
-    tmp = path + ".tmp";
-    cpd::io::write_diff(tmp, g, w);
-    if (::rename(tmp.c_str(), path.c_str()) != 0) {
-        ::unlink(tmp.c_str());
-        throw std::runtime_error("cannot write " + path);
-    }
+    must(cpd_index_get_weights(ix, w.data()));
+    const std::string path = qfile + ".diff", tmp = path + ".tmp";
+    cpd::io::write_diff(tmp, g, w);  // the library's writer; a throw leaves its temporary as it is
+    SideFile::place(true, tmp, path);
 }
 
 // What follows the common fields on an .assign line: the rule's step and gap terms.
@@ -365,8 +367,7 @@ static double run_assign(int (*loop)(cpd_index*, const cpd_search_opts*, uint64_
                          const cpd_vdf& vdf, uint32_t iters, std::vector<std::string>& lines) {
     std::vector<Rec> it(iters);
     uint32_t made = 0;
-    if (loop(ix, &so, 0, nullptr, cap.data(), &vdf, iters, it.data(), &made) != CPD_OK)
-        throw std::runtime_error(cpd_last_error());
+    must(loop(ix, &so, 0, nullptr, cap.data(), &vdf, iters, it.data(), &made));
     double search_ms = 0.0;
     for (uint32_t k = 0; k < made; ++k) {
         const Rec& r = it[k];
@@ -425,21 +426,14 @@ static void write_timed(cpd_index* ix, const std::string& qfile, const std::vect
     std::vector<uint64_t> cost(nq);
     std::vector<uint32_t> hops(nq);
     std::vector<uint8_t> fin(nq);
-    if (cpd_query_timed_fetch(ix, cost.data(), hops.data(), fin.data()) != CPD_OK)
-        throw std::runtime_error(cpd_last_error());
-    const std::string path = qfile + ".res", tmp = path + ".tmp";
-    std::FILE* f = std::fopen(tmp.c_str(), "w");
-    if (!f) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+    must(cpd_query_timed_fetch(ix, cost.data(), hops.data(), fin.data()));
+    SideFile side(qfile + ".res");
     bool ok = true;
     for (size_t q = 0; q < nq && ok; ++q)
-        ok = std::fprintf(f, "%u %u %u %u %llu %llu\n", s[q], t[q], hops[q], fin[q] == 1 ? 1u : 0u,
-                          (unsigned long long)(dep.empty() ? 0 : dep[q]),
+        ok = std::fprintf(side.f, "%u %u %u %u %llu %llu\n", s[q], t[q], hops[q],
+                          fin[q] == 1 ? 1u : 0u, (unsigned long long)(dep.empty() ? 0 : dep[q]),
                           (unsigned long long)cost[q]) > 0;
-    ok = std::fclose(f) == 0 && ok;
-    if (!ok || ::rename(tmp.c_str(), path.c_str()) != 0) {
-        ::unlink(tmp.c_str());
-        throw std::runtime_error("cannot write " + path);
-    }
+    side.commit(ok);
 }
 
 static bool write_answer(const std::string& path, const std::string& line) {
@@ -469,73 +463,87 @@ static bool write_answer(const std::string& path, const std::string& line) {
     return true;
 }
 
-int main(int argc, char** argv) {
+// ---- options ---------------------------------------------------------------
+
+// How every request of this server is answered: the call behind it, those of
+// --alg table-search first, then those of --alg cpd-search.
+enum class Mode { Run, Paths, Costs, Loads, Timed, Search, SearchPaths, SearchLoads, Assign };
+enum class Step { Msa, Line, Conj };  // the --assign loop's step rule
+
+// --alg cpd-search: the answer line carries the search counters
+static bool is_search(Mode m) { return m >= Mode::Search; }
+// the diff field is a list of weight sets, and <query file>.res the mode's own
+// file ("debug": true adds nothing)
+static bool lists_diffs(Mode m) { return m == Mode::Costs || m == Mode::Timed; }
+
+// Everything read from argv; the numbers are in the ranges parse_options checks.
+struct Options {
+    std::vector<std::string> inputs;  // X.xy [DIFF]
+    std::string method, outdir, fifo, index, device;  // device "": worker id modulo the devices
+    long long key = -1, wid = -1, W = -1;
+    int mcode = 0;
+    Mode mode = Mode::Run;
+    bool timed_loads = false;  // --timed with --loads
+    Step step = Step::Msa;
+    long long slice_moves = 0, load_slices = 1, load_slice_moves = 0, period = 0;
+    long long assign_iters = 0, assign_cap = 0;
+    cpd_vdf vdf{3, 20, 4, 1};
+    int read_threads = 8, parse_threads = 16;
+    bool once = false, verbose = false;
+    const std::string& xy() const { return inputs[0]; }
+};
+
+static const char kUsage[] =
+    "usage: fifo_auto --input X.xy [DIFF] --partmethod {div|mod} --partkey K --workerid I --maxworker W --outdir D --alg table-search|cpd-search\n"
+    "       [--paths]  table-search only: answer through cpd_query_paths and write every\n"
+    "                  walk's nodes to <query file>.paths, one line per query:\n"
+    "                  s t finished n v0 ... v(n-1)\n"
+    "       [--search-paths]  cpd-search only: answer through cpd_query_search_paths and\n"
+    "                  write every route's nodes to <query file>.paths, same format\n"
+    "       [--search-loads]  cpd-search only: answer through cpd_query_search_loads (demand 1\n"
+    "                  per query) and write every loaded edge of the routes found to\n"
+    "                  <query file>.loads: edge from to load\n"
+    "       [--costs [--slice-moves S]]  table-search only: the request's diff field may list\n"
+    "                  up to 8 diffs (\"-,a.diff,b.diff\"); one walk costs every query under each\n"
+    "                  (cpd_query_costs) and <query file>.res gets, per query:\n"
+    "                  s t moves finished cost_0 ... cost_{C-1}\n"
+    "                  (with --slice-moves S one cost: move h under diff min(h / S, last));\n"
+    "                  \"debug\": true in a request adds nothing: .res is the costs file\n"
+    "       [--loads [--load-slices K --load-slice-moves S]]  table-search only: answer through\n"
+    "                  cpd_query_loads (demand 1 per query) and write every loaded edge to\n"
+    "                  <query file>.loads: edge from to load_0 ... load_{K-1}\n"
+    "                  (K slices: move h counts in slice min(h / S, K - 1))\n"
+    "       [--timed P [--loads]]  table-search only: answer through cpd_query_timed; the\n"
+    "                  request's diff field lists up to 8 diffs, diff j the network during clock\n"
+    "                  time [j P, (j + 1) P); departures from <query file>.dep (one per query\n"
+    "                  line; absent: 0); <query file>.res gets, per query:\n"
+    "                  s t moves finished depart cost\n"
+    "                  (with --loads <query file>.loads has one column per diff)\n"
+    "       [--assign K --capacity C [--vdf A/B^P]]  cpd-search only: answer through\n"
+    "                  cpd_query_assign (K iterations, demand 1 per query, every edge at capacity C,\n"
+    "                  delay w0 (1 + A/B (x/C)^P), default 3/20^4); writes <query file>.loads,\n"
+    "                  .assign (k finished sptt tstt moves changed) and .diff (the final weights)\n"
+    "       [--step msa|line|conj]  with --assign: msa (default) as above; line answers through\n"
+    "                  cpd_query_assign_line (the line-search step): .assign lines end in\n"
+    "                  lambda g0 xw0, .loads holds the final flow's volumes; conj answers through\n"
+    "                  cpd_query_assign_conj (the conjugate step): .assign lines end in lambda gy xw0 alpha\n";
+
+// How every check below refuses: its text on stderr, exit status 2.
+static int refuse(const char* text) {
+    std::fputs(text, stderr);
+    return 2;
+}
+
+// Fills `o` from argv.  The checks run in this order, before anything is read
+// or made; returns the exit status of the first that fails, or -1 to go on.
+static int parse_options(int argc, char** argv, Options& o) {
     cli::Args a(argc, argv);
-    const auto& inputs = a.list("input");
-    std::string method = a.str_any({"partmethod", "partition"});
-    long long key = a.num("partkey", -1), wid = a.num("workerid", -1), W = a.num("maxworker", -1);
-    std::string alg = a.str("alg", "table-search");
-    if (inputs.empty() || method.empty() || key <= 0 || wid < 0 || W <= 0 || wid >= W) {
-        std::fprintf(stderr,
-                     "usage: fifo_auto --input X.xy [DIFF] --partmethod {div|mod} --partkey K "
-                     "--workerid I --maxworker W --outdir D --alg table-search|cpd-search\n"
-                     "       [--paths]  table-search only: answer through cpd_query_paths and "
-                     "write every\n"
-                     "                  walk's nodes to <query file>.paths, one line per query:\n"
-                     "                  s t finished n v0 ... v(n-1)\n"
-                     "       [--search-paths]  cpd-search only: answer through "
-                     "cpd_query_search_paths and\n"
-                     "                  write every route's nodes to <query file>.paths, same "
-                     "format\n"
-                     "       [--search-loads]  cpd-search only: answer through "
-                     "cpd_query_search_loads (demand 1\n"
-                     "                  per query) and write every loaded edge of the routes "
-                     "found to\n"
-                     "                  <query file>.loads: edge from to load\n"
-                     "       [--costs [--slice-moves S]]  table-search only: the request's diff "
-                     "field may list\n"
-                     "                  up to 8 diffs (\"-,a.diff,b.diff\"); one walk costs every "
-                     "query under each\n"
-                     "                  (cpd_query_costs) and <query file>.res gets, per query:\n"
-                     "                  s t moves finished cost_0 ... cost_{C-1}\n"
-                     "                  (with --slice-moves S one cost: move h under diff "
-                     "min(h / S, last));\n"
-                     "                  \"debug\": true in a request adds nothing: .res is the "
-                     "costs file\n"
-                     "       [--loads [--load-slices K --load-slice-moves S]]  table-search only: "
-                     "answer through\n"
-                     "                  cpd_query_loads (demand 1 per query) and write every "
-                     "loaded edge to\n"
-                     "                  <query file>.loads: edge from to load_0 ... load_{K-1}\n"
-                     "                  (K slices: move h counts in slice min(h / S, K - 1))\n"
-                     "       [--timed P [--loads]]  table-search only: answer through "
-                     "cpd_query_timed; the\n"
-                     "                  request's diff field lists up to 8 diffs, diff j the "
-                     "network during clock\n"
-                     "                  time [j P, (j + 1) P); departures from <query file>.dep "
-                     "(one per query\n"
-                     "                  line; absent: 0); <query file>.res gets, per query:\n"
-                     "                  s t moves finished depart cost\n"
-                     "                  (with --loads <query file>.loads has one column per "
-                     "diff)\n"
-                     "       [--assign K --capacity C [--vdf A/B^P]]  cpd-search only: answer "
-                     "through\n"
-                     "                  cpd_query_assign (K iterations, demand 1 per query, every "
-                     "edge at capacity C,\n"
-                     "                  delay w0 (1 + A/B (x/C)^P), default 3/20^4); writes <query "
-                     "file>.loads,\n"
-                     "                  .assign (k finished sptt tstt moves changed) and .diff (the "
-                     "final weights)\n"
-                     "       [--step msa|line|conj]  with --assign: msa (default) as above; line answers "
-                     "through\n"
-                     "                  cpd_query_assign_line (the line-search step): .assign lines "
-                     "end in\n"
-                     "                  lambda g0 xw0, .loads holds the final flow's volumes; conj "
-                     "answers through\n"
-                     "                  cpd_query_assign_conj (the conjugate step): .assign lines "
-                     "end in lambda gy xw0 alpha\n");
-        return 2;
-    }
+    o.inputs = a.list("input");
+    o.method = a.str_any({"partmethod", "partition"});
+    o.key = a.num("partkey", -1), o.wid = a.num("workerid", -1), o.W = a.num("maxworker", -1);
+    const std::string alg = a.str("alg", "table-search");
+    if (o.inputs.empty() || o.method.empty() || o.key <= 0 || o.wid < 0 || o.W <= 0 || o.wid >= o.W)
+        return refuse(kUsage);
     // table-search (make_fifos.py:20) or the CPD-heuristic search
     // (cpd_query_search; args.py:29-57)
     const bool search = alg == "cpd-search" || alg == "cpd_search";
@@ -545,534 +553,637 @@ int main(int argc, char** argv) {
         return 2;
     }
     const bool paths = a.has("paths");
-    if (paths && search) {
-        std::fprintf(stderr, "fifo_auto: --paths needs --alg table-search (the paths of a "
-                             "cpd-search are extracted with --search-paths)\n");
-        return 2;
-    }
+    if (paths && search)
+        return refuse("fifo_auto: --paths needs --alg table-search (the paths of a "
+                      "cpd-search are extracted with --search-paths)\n");
     const bool search_paths = a.has("search-paths");
-    if (search_paths && !search) {
-        std::fprintf(stderr, "fifo_auto: --search-paths needs --alg cpd-search (the walks of a "
-                             "table-search are extracted with --paths)\n");
-        return 2;
-    }
+    if (search_paths && !search)
+        return refuse("fifo_auto: --search-paths needs --alg cpd-search (the walks of a "
+                      "table-search are extracted with --paths)\n");
     const bool costs = a.has("costs");
-    if (costs && (search || paths)) {
-        std::fprintf(stderr, "fifo_auto: --costs needs --alg table-search without --paths (a "
-                             "cpd-search's route depends on the weights; --paths answers through "
-                             "cpd_query_paths)\n");
-        return 2;
-    }
-    const long long slice_moves = a.num("slice-moves", 0);
-    if ((slice_moves && !costs) || slice_moves < 0 || slice_moves > 0xFFFFFFFFll) {
-        std::fprintf(stderr, "fifo_auto: --slice-moves S needs --costs and 0 <= S < 2^32\n");
-        return 2;
-    }
+    if (costs && (search || paths))
+        return refuse("fifo_auto: --costs needs --alg table-search without --paths (a "
+                      "cpd-search's route depends on the weights; --paths answers through "
+                      "cpd_query_paths)\n");
+    o.slice_moves = a.num("slice-moves", 0);
+    if ((o.slice_moves && !costs) || o.slice_moves < 0 || o.slice_moves > 0xFFFFFFFFll)
+        return refuse("fifo_auto: --slice-moves S needs --costs and 0 <= S < 2^32\n");
     const bool loads = a.has("loads");
-    if (loads && (search || paths || costs)) {
-        std::fprintf(stderr, "fifo_auto: --loads needs --alg table-search without --paths or "
-                             "--costs (a cpd-search's route is not the walk's: --search-loads loads "
-                             "it; --paths and --costs "
-                             "answer through cpd_query_paths and cpd_query_costs)\n");
-        return 2;
-    }
+    if (loads && (search || paths || costs))
+        return refuse("fifo_auto: --loads needs --alg table-search without --paths or "
+                      "--costs (a cpd-search's route is not the walk's: --search-loads loads "
+                      "it; --paths and --costs "
+                      "answer through cpd_query_paths and cpd_query_costs)\n");
+    const bool slices = a.has("load-slices") || a.has("load-slice-moves");
     const bool timed = a.has("timed");
-    if (timed && (search || paths || costs || a.has("load-slices") || a.has("load-slice-moves"))) {
-        std::fprintf(stderr, "fifo_auto: --timed needs --alg table-search without --paths, --costs, "
-                             "--load-slices or --load-slice-moves (a cpd-search's route is not the "
-                             "walk's; --paths and --costs answer through cpd_query_paths and "
-                             "cpd_query_costs; a timed walk's load planes are its diffs)\n");
-        return 2;
-    }
-    const long long period = a.num("timed", 0);
-    if (timed && (period < 1 || period > (1ll << 60))) {
-        std::fprintf(stderr, "fifo_auto: --timed P needs 1 <= P <= 2^60\n");
-        return 2;
-    }
+    if (timed && (search || paths || costs || slices))
+        return refuse("fifo_auto: --timed needs --alg table-search without --paths, --costs, "
+                      "--load-slices or --load-slice-moves (a cpd-search's route is not the "
+                      "walk's; --paths and --costs answer through cpd_query_paths and "
+                      "cpd_query_costs; a timed walk's load planes are its diffs)\n");
+    o.period = a.num("timed", 0);
+    if (timed && (o.period < 1 || o.period > (1ll << 60)))
+        return refuse("fifo_auto: --timed P needs 1 <= P <= 2^60\n");
     const bool search_loads = a.has("search-loads");
-    if (search_loads && (!search || search_paths || a.has("load-slices") || a.has("load-slice-moves"))) {
-        std::fprintf(stderr, "fifo_auto: --search-loads needs --alg cpd-search without --search-paths, "
-                             "--load-slices or --load-slice-moves (the walks of a table-search are "
-                             "loaded with --loads; --search-paths answers through "
-                             "cpd_query_search_paths; a search loads one plane)\n");
-        return 2;
-    }
-    const long long load_slices = a.num("load-slices", 1), load_slice_moves = a.num("load-slice-moves", 0);
-    if (((a.has("load-slices") || a.has("load-slice-moves")) && !loads) || load_slices < 1 ||
-        load_slices > (long long)CPD_MAX_LOAD_SLICES || load_slice_moves < 0 ||
-        load_slice_moves > 0xFFFFFFFFll || (load_slices == 1) != (load_slice_moves == 0)) {
+    if (search_loads && (!search || search_paths || slices))
+        return refuse("fifo_auto: --search-loads needs --alg cpd-search without --search-paths, "
+                      "--load-slices or --load-slice-moves (the walks of a table-search are "
+                      "loaded with --loads; --search-paths answers through "
+                      "cpd_query_search_paths; a search loads one plane)\n");
+    o.load_slices = a.num("load-slices", 1), o.load_slice_moves = a.num("load-slice-moves", 0);
+    if ((slices && !loads) || o.load_slices < 1 || o.load_slices > (long long)CPD_MAX_LOAD_SLICES ||
+        o.load_slice_moves < 0 || o.load_slice_moves > 0xFFFFFFFFll ||
+        (o.load_slices == 1) != (o.load_slice_moves == 0)) {
         std::fprintf(stderr, "fifo_auto: --load-slices K --load-slice-moves S need --loads, 2 <= K "
                              "<= %u and 0 < S < 2^32 (both or neither)\n", CPD_MAX_LOAD_SLICES);
         return 2;
     }
     const bool assign = a.has("assign");
-    if (assign && (!search || search_paths || search_loads || loads || timed)) {
-        std::fprintf(stderr, "fifo_auto: --assign needs --alg cpd-search without --search-paths, "
-                             "--search-loads, --loads or --timed (the loop answers through "
-                             "cpd_query_assign and writes the loads itself)\n");
-        return 2;
-    }
-    const long long assign_iters = a.num("assign", 0), assign_cap = a.num("capacity", 0);
-    cpd_vdf vdf{3, 20, 4, 1};
-    {
-        const std::string v = a.str("vdf", "3/20^4");
-        unsigned an = 0, ad = 0, pw = 0;
-        char tail = 0;
-        const bool ok = std::sscanf(v.c_str(), "%u/%u^%u%c", &an, &ad, &pw, &tail) == 3 &&
-                        an <= 65535u && ad >= 1u && ad <= 65535u && pw >= 1u && pw <= 4u;
-        if ((a.has("vdf") || a.has("capacity")) && !assign) {
-            std::fprintf(stderr, "fifo_auto: --capacity and --vdf need --assign\n");
-            return 2;
-        }
-        if (assign && (!ok || assign_iters < 1 || assign_iters > 65535 || assign_cap < 1 ||
-                       assign_cap > 0xFFFFFFFFll)) {
-            std::fprintf(stderr, "fifo_auto: --assign K --capacity C [--vdf A/B^P] need 1 <= K <= "
-                                 "65535, 1 <= C < 2^32, A <= 65535, 1 <= B <= 65535 and 1 <= P <= 4\n");
-            return 2;
-        }
-        vdf = cpd_vdf{an, ad, pw, 1};
-    }
+    if (assign && (!search || search_paths || search_loads || loads || timed))
+        return refuse("fifo_auto: --assign needs --alg cpd-search without --search-paths, "
+                      "--search-loads, --loads or --timed (the loop answers through "
+                      "cpd_query_assign and writes the loads itself)\n");
+    o.assign_iters = a.num("assign", 0), o.assign_cap = a.num("capacity", 0);
+    unsigned an = 0, ad = 0, pw = 0;
+    char tail = 0;
+    const bool vdf_ok =
+        std::sscanf(a.str("vdf", "3/20^4").c_str(), "%u/%u^%u%c", &an, &ad, &pw, &tail) == 3 &&
+        an <= 65535u && ad >= 1u && ad <= 65535u && pw >= 1u && pw <= 4u;
+    if ((a.has("vdf") || a.has("capacity")) && !assign)
+        return refuse("fifo_auto: --capacity and --vdf need --assign\n");
+    if (assign && (!vdf_ok || o.assign_iters < 1 || o.assign_iters > 65535 || o.assign_cap < 1 ||
+                   o.assign_cap > 0xFFFFFFFFll))
+        return refuse("fifo_auto: --assign K --capacity C [--vdf A/B^P] need 1 <= K <= "
+                      "65535, 1 <= C < 2^32, A <= 65535, 1 <= B <= 65535 and 1 <= P <= 4\n");
+    o.vdf = cpd_vdf{an, ad, pw, 1};
     const std::string step = a.str("step", "msa");
-    if ((a.has("step") && !assign) || (step != "msa" && step != "line" && step != "conj")) {
-        std::fprintf(stderr, "fifo_auto: --step msa|line|conj needs --assign\n");
-        return 2;
-    }
-    const bool step_line = step == "line", step_conj = step == "conj";
-    int mcode = cli::method_code(method);
-    std::string xy = inputs[0];
-    std::string outdir = a.str("outdir", ".");
-    std::string fifo = a.str("fifo", "/tmp/worker" + std::to_string(wid) + ".fifo");
-    bool once = a.has("once");
+    if ((a.has("step") && !assign) || (step != "msa" && step != "line" && step != "conj"))
+        return refuse("fifo_auto: --step msa|line|conj needs --assign\n");
+    o.step = step == "line" ? Step::Line : step == "conj" ? Step::Conj : Step::Msa;
+    o.mcode = cli::method_code(o.method);
+    // what passed the checks names one way of answering
+    o.mode = assign         ? Mode::Assign
+             : search_paths ? Mode::SearchPaths
+             : search_loads ? Mode::SearchLoads
+             : search       ? Mode::Search
+             : costs        ? Mode::Costs
+             : timed        ? Mode::Timed
+             : loads        ? Mode::Loads
+             : paths        ? Mode::Paths
+                            : Mode::Run;
+    o.timed_loads = timed && loads;
+    o.outdir = a.str("outdir", ".");
+    o.fifo = a.str("fifo", "/tmp/worker" + std::to_string(o.wid) + ".fifo");
+    o.index = a.str("index", "auto");
+    o.device = a.str("device");
+    o.read_threads = (int)a.num("read-threads", 8);
     // threads parsing a request's query file (a 1M-query file is ~14 MB)
-    const int parse_threads = (int)a.num("parse-threads", 16);
-    const bool verbose = a.has("verbose");
+    o.parse_threads = (int)a.num("parse-threads", 16);
+    o.once = a.has("once");
+    o.verbose = a.has("verbose");
+    return -1;
+}
+
+// ---- start-up load ---------------------------------------------------------
+
+// The request FIFO exists before the (possibly long) index load: a request
+// sent meanwhile blocks in its writer's open() until the serve loop reads it,
+// instead of `cat <<CONF > fifo` creating a regular file there.  A non-FIFO
+// left at the path (such a file from an earlier run) is replaced.
+static bool make_fifo(const std::string& fifo) {
+    struct stat st;
+    if (::lstat(fifo.c_str(), &st) == 0 && !S_ISFIFO(st.st_mode)) ::unlink(fifo.c_str());
+    if (::mkfifo(fifo.c_str(), 0666) != 0 && errno != EEXIST) {
+        std::fprintf(stderr, "fifo_auto: mkfifo %s: %s\n", fifo.c_str(), std::strerror(errno));
+        return false;
+    }
+    if (::lstat(fifo.c_str(), &st) == 0 && S_ISFIFO(st.st_mode)) return true;
+    std::fprintf(stderr, "fifo_auto: %s is not a FIFO\n", fifo.c_str());
+    return false;
+}
+
+// What the load leaves for the serve loop; unload() frees it.
+struct Loaded {
+    cpd_plan* plan = nullptr;
+    cpd_graph* dg = nullptr;
+    cpd_index* ix = nullptr;
+    cpd::io::XYGraph g;
+    std::map<std::string, std::vector<uint32_t>> diff_cache;
+    int device = -1;
+    bool arena = false;
+};
+
+static void unload(Loaded& L) {
+    cpd_index_free(L.ix);
+    cpd_graph_free(L.dg);
+    cpd_plan_free(L.plan);
+    if (L.arena) cpd_device_arena_release(L.device);
+}
+
+// The weights a diff file gives the graph's edges, read once per name.
+static const std::vector<uint32_t>& diff_weights(Loaded& L, const std::string& name) {
+    auto it = L.diff_cache.find(name);
+    if (it == L.diff_cache.end()) it = L.diff_cache.emplace(name, cpd::io::read_diff(name, L.g)).first;
+    return it->second;
+}
+
+// This worker's buckets, headers only (targets, run counts or offsets), in
+// bucket order: formats[k] says whether heads[k] or mheads[k] is filled.
+struct Heads {
+    uint32_t n0 = 0;  // the node count, from the order file
+    std::vector<std::string> paths;
+    std::vector<int> formats;  // 1: run words; 2: compact move tables
+    std::vector<cpd::io::CpdBucket> heads;
+    std::vector<cpd::io::MoveBucket> mheads;
+    std::vector<uint32_t> targets;
+    uint64_t total_runs = 0, compact_bytes = 0;
+    uint32_t move_bits = 0;  // the compact rows' width (0: some bucket holds run words)
+    bool all_compact = true;
+};
+
+// DOSCPD02/03 (compact move tables, what make_cpd_auto writes by default) or
+// DOSCPD01 (run words).  The node count comes from the order file
+// make_cpd_auto wrote beside them; the graph's fingerprint is checked once the
+// .xy is read.
+static Heads read_heads(const Options& o) {
+    Heads h;
+    h.n0 = cpd::io::read_order_n(cpd::io::order_path(o.outdir, o.xy()));
+    uint32_t nb = 0;
+    cli::check(cpd_partition_nbuckets(h.n0, o.mcode, (uint32_t)o.key, &nb), "buckets");
+    for (uint32_t b = 0; b < nb; ++b) {
+        if (b % (uint32_t)o.W != (uint32_t)o.wid) continue;
+        h.paths.push_back(cpd::io::bucket_path(o.outdir, o.xy(), o.method, (uint32_t)o.key, b));
+        h.formats.push_back(cpd::io::bucket_format(h.paths.back()));
+        if (h.formats.back() == 1) {
+            h.heads.push_back(cpd::io::read_bucket_head(h.paths.back()));
+            h.mheads.emplace_back();
+            const auto& bk = h.heads.back();
+            h.targets.insert(h.targets.end(), bk.targets.begin(), bk.targets.end());
+            h.total_runs += bk.offsets.back();
+            h.all_compact = false;
+        } else {
+            h.mheads.push_back(cpd::io::read_move_bucket_head(h.paths.back()));
+            h.heads.emplace_back();
+            const auto& bk = h.mheads.back();
+            if (bk.n != h.n0) throw std::runtime_error("bucket " + std::to_string(b) + " has another node count");
+            h.targets.insert(h.targets.end(), bk.targets.begin(), bk.targets.end());
+            h.total_runs += bk.total_runs;
+            h.compact_bytes += 4ull * bk.words * bk.targets.size();
+            h.move_bits = bk.bits;
+        }
+    }
+    return h;
+}
+
+// The device side, started on a thread beside the host reads (VERDICT r04
+// item 7): the first HIP call and, for compact buckets, the dense index's HBM
+// committed as an arena (nrows x n padded to 2048 columns x bits / 8 bytes:
+// committing fresh HBM costs about a second per 30 GB) that
+// cpd_index_create_empty then carves.  Joined by the caller, or on the way
+// out; `o` and `h` outlive it.
+struct DeviceStart {
+    int ndev = 0, rc = CPD_OK, device = -1;
+    bool arena = false;
+    double seconds = 0.0;
+    std::string err;
+    std::thread thr;
+    DeviceStart(const Options& o, const Heads& h) : thr([this, &o, &h] { run(o, h); }) {}
+    ~DeviceStart() {
+        if (thr.joinable()) thr.join();
+    }
+    void run(const Options& o, const Heads& h) {
+        const double td = now();
+        rc = cpd_device_count(&ndev);
+        if (rc == CPD_OK && ndev > 0) {
+            device = (int)(o.device.empty() ? o.wid % ndev : std::atoll(o.device.c_str()));
+            if (h.all_compact && !h.targets.empty() && h.move_bits) {
+                const uint64_t npad = (h.n0 + 2047ull) / 2048ull * 2048ull;
+                const uint64_t bytes = (uint64_t)h.targets.size() * (npad * h.move_bits / 32ull) * 4ull;
+                // only for an index that will be dense (--index rle keeps
+                // runs; auto takes tables when the runs weigh more — the
+                // index's own test): an unused arena would hold HBM the
+                // search workspace is sized from
+                const bool dense = o.index == "dense" || (o.index != "rle" && 4ull * h.total_runs > bytes);
+                if (dense) arena = cpd_device_arena(device, bytes + (1ull << 20), 0) == CPD_OK;
+            }
+        }
+        if (rc != CPD_OK) err = cpd_last_error();
+        seconds = now() - td;
+    }
+};
+
+// The graph, the plan, the start diff's weights, and the checks that the index
+// on disk is this graph's: the stored column order against this build's, and
+// every bucket's fingerprint, key and method.
+static void load_graph(const Options& o, const Heads& h, Loaded& L) {
+    const cpd::io::XYGraph& g = L.g = cpd::io::read_xy(o.xy());
+    const uint64_t fp = cpd::io::graph_fingerprint(g.n, g.row_ptr.data(), g.dst.data(), g.w.data());
+    if (o.inputs.size() > 1) diff_weights(L, o.inputs[1]);
+    cpd_plan_opts po{};
+    po.no_hierarchy = 1;  // queries need the CSR + column order only
+    cli::check(cpd_plan_create(g.row_ptr.data(), g.dst.data(), g.w.data(), g.n, g.m, &po, &L.plan),
+               "plan");
+    std::vector<uint32_t> order(g.n);
+    cli::check(cpd_plan_order(L.plan, order.data()), "order");
+    if (cpd::io::read_order(cpd::io::order_path(o.outdir, o.xy()), fp) != order)
+        throw std::runtime_error("stored column order differs from this build's");
+    for (size_t k = 0; k < h.paths.size(); ++k) {
+        const bool rle = h.formats[k] == 1;
+        const uint64_t bfp = rle ? h.heads[k].fingerprint : h.mheads[k].fingerprint;
+        const uint32_t bkey = rle ? h.heads[k].key : h.mheads[k].key;
+        const uint32_t bmethod = rle ? h.heads[k].method : h.mheads[k].method;
+        if (bfp != fp || bkey != (uint32_t)o.key || bmethod != (uint32_t)o.mcode)
+            throw std::runtime_error(h.paths[k] + " was built for another graph/partition");
+    }
+}
+
+// The rows are streamed in pieces of <= kPiece words (a longer row alone): a
+// dense index never holds the worker's runs in HBM or RAM.
+constexpr uint64_t kPiece = 64ull << 20;  // 256 MB
+
+// The two page-locked buffers the compact pieces are read into.
+struct PinnedPair {
+    uint32_t* p[2] = {nullptr, nullptr};
+    uint64_t bytes = 0;
+    PinnedPair() = default;
+    PinnedPair(const PinnedPair&) = delete;
+    ~PinnedPair() {
+        for (auto q : p) cpd_host_free(q);
+    }
+};
+
+// One compact bucket: its pieces read into the two buffers by a reader
+// thread while the previous piece is appended (uploaded).
+static void stream_compact(cpd_index* ix, const std::string& path, const cpd::io::MoveBucket& mh,
+                           int read_threads, PinnedPair& pin) {
+    const uint32_t nr = (uint32_t)mh.targets.size();
+    if (!nr) return;
+    const uint32_t per = (uint32_t)std::min<uint64_t>(nr, std::max<uint64_t>(1, kPiece / mh.words));
+    if (4ull * mh.words * per > pin.bytes) {  // grown for this bucket's pieces
+        for (auto& p : pin.p) {
+            cpd_host_free(p);
+            void* q = nullptr;
+            cli::check(cpd_host_alloc(4ull * mh.words * per, &q), "pinned buffer");
+            p = static_cast<uint32_t*>(q);
+        }
+        pin.bytes = 4ull * mh.words * per;
+    }
+    auto read = [&](uint32_t r0, int slot) {
+        cpd::io::read_move_bucket_rows(path, mh, r0, std::min(per, nr - r0), pin.p[slot], read_threads);
+    };
+    std::future<void> rd = std::async(std::launch::async, read, 0u, 0);
+    for (uint32_t r0 = 0, i = 0; r0 < nr; r0 += per, ++i) {
+        rd.get();  // piece i is in pin.p[i & 1] (a read error is rethrown here)
+        if (r0 + per < nr) rd = std::async(std::launch::async, read, r0 + per, (int)((i + 1) & 1u));
+        const int rc = cpd_index_append_moves(ix, std::min(per, nr - r0), mh.bits, pin.p[i & 1u]);
+        if (rc != CPD_OK) {
+            if (rd.valid()) rd.wait();
+            cli::check(rc, "index rows");
+        }
+    }
+}
+
+// One bucket of run words, piece by piece through `buf` (offsets through `rel`).
+static void stream_runs(cpd_index* ix, const std::string& path, const cpd::io::CpdBucket& head,
+                        std::vector<uint32_t>& buf, std::vector<uint64_t>& rel) {
+    const auto& off = head.offsets;
+    const uint32_t nr = (uint32_t)head.targets.size();
+    for (uint32_t r0 = 0; r0 < nr;) {
+        uint32_t r1 = r0 + 1;
+        while (r1 < nr && off[r1 + 1] - off[r0] <= kPiece) ++r1;
+        buf.resize(off[r1] - off[r0]);
+        cpd::io::read_bucket_runs(path, head, off[r0], buf.size(), buf.data());
+        rel.resize(r1 - r0 + 1);
+        for (uint32_t i = r0; i <= r1; ++i) rel[i - r0] = off[i] - off[r0];
+        cli::check(cpd_index_append_rows(ix, r1 - r0, rel.data(), buf.data()), "index rows");
+        r0 = r1;
+    }
+}
+
+// Streams the CPD buckets this worker owns onto its GPU and says so: the
+// machine-readable line (bench.py's full-build leg reads it), then the
+// "listening" line a driver waits for.
+static Loaded load(const Options& o) {
+    Loaded L;
+    const double t0 = now();
+    const Heads h = read_heads(o);
+    DeviceStart dev(o, h);
+    load_graph(o, h, L);
+    const double t_graph0 = now();
+    dev.thr.join();
+    const double t_devwait = now() - t_graph0;
+    if (dev.rc != CPD_OK) throw std::runtime_error("device: " + dev.err);
+    if (dev.ndev == 0) throw std::runtime_error("no GPU visible (this build has no CPU path)");
+    L.device = dev.device;
+    L.arena = dev.arena;
+    cli::check(cpd_graph_create(L.plan, L.device, &L.dg), "graph upload");
+    const int imode = o.index == "rle" ? CPD_INDEX_RLE : o.index == "dense" ? CPD_INDEX_DENSE : CPD_INDEX_AUTO;
+    cli::check(cpd_index_create_empty(L.dg, h.targets.data(), (uint32_t)h.targets.size(), imode,
+                                      h.total_runs, &L.ix),
+               "index");
+    const double t_rows0 = now();
+    {
+        std::vector<uint32_t> buf;
+        std::vector<uint64_t> rel;
+        PinnedPair pin;
+        for (size_t k = 0; k < h.paths.size(); ++k) {
+            if (h.formats[k] == 2) stream_compact(L.ix, h.paths[k], h.mheads[k], o.read_threads, pin);
+            else stream_runs(L.ix, h.paths[k], h.heads[k], buf, rel);
+        }
+    }
+    const double t_rows = now() - t_rows0;
+    int mode = 0;
+    cli::check(cpd_index_get_mode(L.ix, &mode), "index mode");
+    const char* index = mode == CPD_INDEX_DENSE ? "dense" : "rle";
+    std::printf("fifo_auto-json: {\"worker\": %lld, \"rows\": %zu, \"runs\": %llu, "
+                "\"index\": \"%s\", \"compact_bytes\": %llu, \"read_plan_s\": %.3f, "
+                "\"device_s\": %.3f, \"device_wait_s\": %.3f, \"arena\": %s, "
+                "\"graph_s\": %.3f, \"rows_s\": %.3f, \"ready_s\": %.3f}\n",
+                o.wid, h.targets.size(), (unsigned long long)h.total_runs, index,
+                (unsigned long long)h.compact_bytes, t_graph0 - t0, dev.seconds, t_devwait,
+                L.arena ? "true" : "false", t_rows0 - t_graph0, t_rows, now() - t0);
+    std::printf("fifo_auto: worker %lld: %zu rows, %llu runs (%s index) on device %d, ready in "
+                "%.3fs; listening on %s\n",
+                o.wid, h.targets.size(), (unsigned long long)h.total_runs, index, L.device,
+                now() - t0, o.fifo.c_str());
+    std::fflush(stdout);
+    return L;
+}
+
+// ---- a request -------------------------------------------------------------
+
+// One message on the request FIFO, taken apart.
+struct Request {
+    std::string qfile, answer, diff;  // diff: "-" when the third field is absent
+    int k_moves = -1;
+    bool debug = false;
+    cpd_search_opts so{};
+};
+
+// False (and a line on stderr) for a message without a query file and an
+// answer FIFO.  Every key of the config is read once.
+static bool parse_request(const std::string& msg, Request& r) {
+    const size_t nl = msg.find('\n');
+    const std::string conf = msg.substr(0, nl);
+    const std::string rest = nl == std::string::npos ? "" : msg.substr(nl + 1);
+    char qfile[4096] = {0}, answer[4096] = {0}, dname[4096] = {0};
+    const int got = std::sscanf(rest.c_str(), "%4095s %4095s %4095s", qfile, answer, dname);
+    if (got < 2) {
+        std::fprintf(stderr, "fifo_auto: malformed request: %s\n", msg.c_str());
+        return false;
+    }
+    r.qfile = qfile, r.answer = answer, r.diff = got >= 3 ? dname : "-";
+    const std::string km = json_field(conf, "k_moves"), hscale = json_field(conf, "hscale"),
+                      fscale = json_field(conf, "fscale"), itrs = json_field(conf, "itrs"),
+                      time = json_field(conf, "time");
+    r.k_moves = km.empty() ? -1 : std::atoi(km.c_str());
+    r.debug = json_field(conf, "debug") == "true";
+    // cpd-search knobs (process_query.py:149-160): hscale, fscale, time
+    // (ns; args.get_time_ns may send a float), itrs; wall-clock time
+    // limit; the workspace (first-pass columns per lane, escalation,
+    // share of HBM) is the library's policy (capacity 0), the one the
+    // bench measures
+    r.so = cpd_search_opts{1.0, 0.0, r.k_moves, -1, 0, 0, 0, CPD_SEARCH_AUTO, 0.0, 0};
+    if (!hscale.empty()) r.so.hscale = std::atof(hscale.c_str());
+    if (!fscale.empty()) r.so.fscale = std::atof(fscale.c_str());
+    if (!itrs.empty()) r.so.itrs = std::atoll(itrs.c_str());
+    const double tn = std::atof(time.c_str());  // "": 0
+    if (tn > 0) r.so.time_ns = (uint64_t)tn;
+    return true;
+}
+
+// The answer line's 10 fields.  t_receive = query file read + parse + upload
+// and sort on the GPU; t_search = the algorithm's device time (table-search:
+// the walk kernel; cpd-search: the search passes + any table rebuild for new
+// weights), the same meaning for both; t_astar = the A* passes alone (0 for
+// table-search)
+static std::string answer_line(bool search, const cpd_query_stats& st, const cpd_search_stats& ss,
+                               double t_receive) {
+    char buf[512];
+    if (search)
+        std::snprintf(buf, sizeof buf, "%llu,%llu,%llu,%llu,%llu,%llu,%llu,%lld,%lld,%lld",
+                      (unsigned long long)ss.expanded, (unsigned long long)ss.inserted,
+                      (unsigned long long)ss.touched, (unsigned long long)ss.updated,
+                      (unsigned long long)ss.surplus, (unsigned long long)ss.plen,
+                      (unsigned long long)ss.finished, (long long)(t_receive * 1e9),
+                      (long long)(ss.kernel_ms * 1e6),
+                      (long long)((ss.kernel_ms + ss.tables_ms) * 1e6));
+    else
+        std::snprintf(buf, sizeof buf, "%llu,0,0,0,0,%llu,%llu,%lld,0,%lld",
+                      (unsigned long long)st.hops, (unsigned long long)st.hops,
+                      (unsigned long long)st.finished, (long long)(t_receive * 1e9),
+                      (long long)(st.kernel_ms * 1e6));
+    return buf;
+}
+
+// <query file>.res of a "debug": true request: s t cost moves finished per
+// query.  Written in place, and a file that cannot be opened is passed over.
+static void write_debug_res(cpd_index* ix, const std::string& qfile, const std::vector<uint32_t>& s,
+                            const std::vector<uint32_t>& t) {
+    const size_t nq = s.size();
+    std::vector<uint64_t> cost(nq);
+    std::vector<uint32_t> hops(nq);
+    std::vector<uint8_t> fin(nq);
+    cli::check(cpd_query_fetch(ix, cost.data(), hops.data(), fin.data()), "fetch");
+    std::FILE* f = std::fopen((qfile + ".res").c_str(), "w");
+    if (!f) return;
+    for (size_t i = 0; i < nq; ++i)
+        std::fprintf(f, "%u %u %llu %u %u\n", s[i], t[i], (unsigned long long)cost[i], hops[i],
+                     fin[i] == 1 ? 1u : 0u);
+    std::fclose(f);
+}
+
+// The serve loop's state: which weights are active on the index, and the
+// request buffers — allocated once and reused by every request, so that their
+// pages stay mapped (a 1M-query file is ~14 MB of them).
+struct Server {
+    const Options& o;
+    Loaded& L;
+    std::string active_diff = "-";
+    std::string active_sets;  // Costs, Timed: the diff list whose sets are loaded
+    size_t active_nsets = 0;
+    std::vector<uint32_t> s, t, cap;
+    std::vector<uint64_t> dep, off;  // departures; path offsets
+
+    Server(const Options& o, Loaded& L) : o(o), L(L) {}
+    void set_weights(const std::string& diff);
+    void assign(const Request& r, cpd_search_stats& ss);
+    void compute(const Request& r, cpd_query_stats& st, cpd_search_stats& ss);
+    std::string answer(const Request& r);  // the answer line; all zeros for a request that failed
+};
+
+// The request's weights, set when they are not the active ones: the one diff
+// ("-": the .xy file's) on the index, or for Costs and Timed the list's sets,
+// loaded beside (and independent of) the index's current weights.
+void Server::set_weights(const std::string& diff) {
+    if (!lists_diffs(o.mode)) {
+        if (diff == active_diff) return;
+        cli::check(cpd_index_set_weights(L.ix, diff == "-" ? nullptr : diff_weights(L, diff).data()),
+                   "weights");
+        active_diff = diff;
+        return;
+    }
+    if (diff == active_sets) return;
+    std::vector<const uint32_t*> sets;
+    for (size_t p0 = 0; p0 <= diff.size();) {
+        size_t p1 = diff.find(',', p0);
+        if (p1 == std::string::npos) p1 = diff.size();
+        const std::string name = diff.substr(p0, p1 - p0);
+        if (name.empty()) throw std::runtime_error("empty name in diff list '" + diff + "'");
+        if (sets.size() == CPD_MAX_WEIGHT_SETS)
+            throw std::runtime_error("more than " + std::to_string(CPD_MAX_WEIGHT_SETS) +
+                                     " diffs in '" + diff + "'");
+        sets.push_back(name == "-" ? nullptr : diff_weights(L, name).data());
+        p0 = p1 + 1;
+    }
+    active_sets.clear();  // a failed call leaves nothing active
+    must(cpd_index_set_weight_sets(L.ix, (uint32_t)sets.size(), sets.data()));
+    active_sets = diff;
+    active_nsets = sets.size();
+}
+
+// An --assign request: the loop, its side files, and the answer line's sums
+// from the last iteration's search.
+void Server::assign(const Request& r, cpd_search_stats& ss) {
+    const size_t nq = s.size();
+    // the loop leaves w_{K+1} on the index: the next request sets its diff's
+    // weights again, whatever its name
+    active_diff.clear();
+    cap.assign(L.g.m, (uint32_t)o.assign_cap);
+    const uint32_t iters = (uint32_t)o.assign_iters;
+    std::vector<std::string> lines;
+    const double search_ms =
+        o.step == Step::Line   ? run_assign<cpd_assign_line_iter>(cpd_query_assign_line, L.ix, r.so, cap,
+                                                                  o.vdf, iters, lines)
+        : o.step == Step::Conj ? run_assign<cpd_assign_conj_iter>(cpd_query_assign_conj, L.ix, r.so, cap,
+                                                                  o.vdf, iters, lines)
+                               : run_assign<cpd_assign_iter>(assign_msa, L.ix, r.so, cap, o.vdf, iters, lines);
+    if (o.step == Step::Msa) write_loads(L.ix, r.qfile, L.g, 1);
+    else write_flow(L.ix, r.qfile, L.g);
+    write_assign(L.ix, r.qfile, L.g, lines);
+    std::vector<uint32_t> cnt(5 * nq), plen(nq);
+    std::vector<uint8_t> fin(nq);
+    if (nq) cli::check(cpd_query_search_counters(L.ix, cnt.data()), "counters");
+    cli::check(cpd_query_fetch(L.ix, nullptr, plen.data(), fin.data()), "fetch");
+    uint64_t* sums[5] = {&ss.expanded, &ss.inserted, &ss.touched, &ss.updated, &ss.surplus};
+    for (size_t q = 0; q < nq; ++q) {
+        for (int k = 0; k < 5; ++k) *sums[k] += cnt[5 * q + k];
+        if (fin[q] == 1) {
+            ss.plen += plen[q];
+            ss.finished++;
+        } else if (fin[q] == 2) {
+            ss.overflow++;
+        }
+    }
+    ss.tables_ms = 0.0;
+    ss.kernel_ms = search_ms;  // tables included
+}
+
+// The mode's call on the prepared queries, then its side files.
+void Server::compute(const Request& r, cpd_query_stats& st, cpd_search_stats& ss) {
+    cpd_index* ix = L.ix;
+    const std::string& qf = r.qfile;
+    switch (o.mode) {
+    case Mode::Assign:
+        assign(r, ss);
+        break;
+    case Mode::Search:
+        must(cpd_query_search(ix, &r.so, &ss));
+        break;
+    case Mode::SearchPaths:
+        off.resize(s.size() + 1);
+        must(cpd_query_search_paths(ix, &r.so, 0, off.data(), &ss, nullptr));
+        write_paths(ix, qf, s, t, off);
+        break;
+    case Mode::SearchLoads:
+        must(cpd_query_search_loads(ix, &r.so, 0, nullptr, 0, &ss, nullptr));
+        write_loads(ix, qf, L.g, 1);
+        break;
+    case Mode::Costs:
+        must(cpd_query_costs(ix, r.k_moves, (uint32_t)o.slice_moves, &st));
+        write_costs(ix, qf, s, t, o.slice_moves ? 1u : active_nsets);
+        break;
+    case Mode::Timed:
+        must(cpd_query_timed(ix, r.k_moves, dep.empty() ? nullptr : dep.data(), (uint64_t)o.period,
+                             nullptr, o.timed_loads ? CPD_TIMED_LOADS : 0u, &st));
+        write_timed(ix, qf, s, t, dep);
+        if (o.timed_loads) write_loads(ix, qf, L.g, active_nsets);
+        break;
+    case Mode::Loads:
+        must(cpd_query_loads(ix, r.k_moves, nullptr, (uint32_t)o.load_slices,
+                             (uint32_t)o.load_slice_moves, 0, &st));
+        write_loads(ix, qf, L.g, (size_t)o.load_slices);
+        break;
+    case Mode::Paths:
+        off.resize(s.size() + 1);
+        must(cpd_query_paths(ix, r.k_moves, off.data(), &st));
+        write_paths(ix, qf, s, t, off);
+        break;
+    case Mode::Run:
+        must(cpd_query_run(ix, r.k_moves, &st));
+        break;
+    }
+}
+
+std::string Server::answer(const Request& r) {
+    std::string line = "0,0,0,0,0,0,0,0,0,0";
+    try {
+        const double t0 = now();
+        cpd::io::read_query_file(r.qfile, o.parse_threads, s, t);
+        if (o.mode == Mode::Timed) read_departures(r.qfile, s.size(), dep);
+        const double t_read = now() - t0;
+        set_weights(r.diff);
+        must(cpd_query_prepare(L.ix, s.data(), t.data(), (uint32_t)s.size()));
+        const double t_receive = now() - t0;
+        cpd_query_stats st{};
+        cpd_search_stats ss{};
+        compute(r, st, ss);
+        if (ss.overflow)
+            std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
+                         (unsigned long long)ss.overflow);
+        if (r.debug && !lists_diffs(o.mode)) write_debug_res(L.ix, r.qfile, s, t);
+        const bool search = is_search(o.mode);
+        line = answer_line(search, st, ss, t_receive);
+        if (o.verbose)  // the receive phase split (stderr: nothing reads stdout by then)
+            std::fprintf(stderr, "fifo_auto-req: {\"queries\": %zu, \"read_parse_s\": %.6f, "
+                         "\"prepare_s\": %.6f, \"compute_s\": %.6f}\n", s.size(), t_read,
+                         t_receive - t_read, search ? ss.kernel_ms * 1e-3 : st.kernel_ms * 1e-3);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "fifo_auto: request failed: %s\n", e.what());
+    }
+    return line;
+}
+
+int main(int argc, char** argv) {
+    Options o;
+    if (const int rc = parse_options(argc, argv, o); rc >= 0) return rc;
     signal(SIGINT, on_signal);
     signal(SIGTERM, on_signal);
     signal(SIGPIPE, SIG_IGN);
-
-    // The request FIFO exists before the (possibly long) index load: a request
-    // sent meanwhile blocks in its writer's open() until the loop below reads
-    // it, instead of `cat <<CONF > fifo` creating a regular file there.  A
-    // non-FIFO left at the path (such a file from an earlier run) is replaced.
-    {
-        struct stat st;
-        if (::lstat(fifo.c_str(), &st) == 0 && !S_ISFIFO(st.st_mode)) ::unlink(fifo.c_str());
-        if (::mkfifo(fifo.c_str(), 0666) != 0 && errno != EEXIST) {
-            std::fprintf(stderr, "fifo_auto: mkfifo %s: %s\n", fifo.c_str(), std::strerror(errno));
-            return 1;
-        }
-        if (::lstat(fifo.c_str(), &st) != 0 || !S_ISFIFO(st.st_mode)) {
-            std::fprintf(stderr, "fifo_auto: %s is not a FIFO\n", fifo.c_str());
-            return 1;
-        }
-    }
-
-    cpd_index* ix = nullptr;
-    cpd_graph* dg = nullptr;
-    cpd_plan* plan = nullptr;
-    cpd::io::XYGraph g;
-    std::map<std::string, std::vector<uint32_t>> diff_cache;
-    std::string active_diff = "-";
-    std::string active_sets;  // --costs: the diff list whose sets are loaded
-    size_t active_nsets = 0;
-    int device = -1;
-    bool arena = false;
+    if (!make_fifo(o.fifo)) return 1;
+    Loaded L;
     try {
-        double t0 = now();
-        // This worker's buckets, headers first (targets, run counts or
-        // offsets): DOSCPD02/03 (compact move tables, what make_cpd_auto
-        // writes by default) or DOSCPD01 (run words).  The node count comes
-        // from the order file make_cpd_auto wrote beside them; the graph's
-        // fingerprint is checked once the .xy is read.
-        const uint32_t n0 = cpd::io::read_order_n(cpd::io::order_path(outdir, xy));
-        uint32_t nb = 0;
-        cli::check(cpd_partition_nbuckets(n0, mcode, (uint32_t)key, &nb), "buckets");
-        std::vector<std::string> paths;
-        std::vector<int> formats;
-        std::vector<cpd::io::CpdBucket> heads;
-        std::vector<cpd::io::MoveBucket> mheads;
-        std::vector<uint32_t> targets;
-        uint64_t total_runs = 0, compact_bytes = 0;
-        uint32_t move_bits = 0;  // the compact rows' width (0: some bucket holds run words)
-        bool all_compact = true;
-        for (uint32_t b = 0; b < nb; ++b) {
-            if (b % (uint32_t)W != (uint32_t)wid) continue;
-            paths.push_back(cpd::io::bucket_path(outdir, xy, method, (uint32_t)key, b));
-            formats.push_back(cpd::io::bucket_format(paths.back()));
-            if (formats.back() == 1) {
-                heads.push_back(cpd::io::read_bucket_head(paths.back()));
-                mheads.emplace_back();
-                const auto& bk = heads.back();
-                targets.insert(targets.end(), bk.targets.begin(), bk.targets.end());
-                total_runs += bk.offsets.back();
-                all_compact = false;
-            } else {
-                mheads.push_back(cpd::io::read_move_bucket_head(paths.back()));
-                heads.emplace_back();
-                const auto& bk = mheads.back();
-                if (bk.n != n0) throw std::runtime_error("bucket " + std::to_string(b) + " has another node count");
-                targets.insert(targets.end(), bk.targets.begin(), bk.targets.end());
-                total_runs += bk.total_runs;
-                compact_bytes += 4ull * bk.words * bk.targets.size();
-                move_bits = bk.bits;
-            }
-        }
-        // The device side starts now, on a thread, beside the host reads
-        // (VERDICT r04 item 7): the first HIP call and, for compact buckets,
-        // the dense index's HBM committed as an arena (nrows x n padded to
-        // 2048 columns x bits / 8 bytes: committing fresh HBM costs about a
-        // second per 30 GB) that cpd_index_create_empty then carves.
-        int ndev = 0;
-        double t_dev = 0.0;
-        int dev_rc = CPD_OK;
-        std::string dev_err;
-        std::thread dev_thr([&] {
-            const double td = now();
-            dev_rc = cpd_device_count(&ndev);
-            if (dev_rc == CPD_OK && ndev > 0) {
-                device = (int)a.num("device", wid % ndev);
-                if (all_compact && !targets.empty() && move_bits) {
-                    const uint64_t npad = (n0 + 2047ull) / 2048ull * 2048ull;
-                    const uint64_t bytes = (uint64_t)targets.size() * (npad * move_bits / 32ull) * 4ull;
-                    // only for an index that will be dense (--index rle keeps
-                    // runs; auto takes tables when the runs weigh more — the
-                    // index's own test): an unused arena would hold HBM the
-                    // search workspace is sized from
-                    const std::string im0 = a.str("index", "auto");
-                    const bool dense = im0 == "dense" || (im0 != "rle" && 4ull * total_runs > bytes);
-                    if (dense) arena = cpd_device_arena(device, bytes + (1ull << 20), 0) == CPD_OK;
-                }
-            }
-            if (dev_rc != CPD_OK) dev_err = cpd_last_error();
-            t_dev = now() - td;
-        });
-        struct Join {
-            std::thread& t;
-            ~Join() {
-                if (t.joinable()) t.join();
-            }
-        } join{dev_thr};
-        g = cpd::io::read_xy(xy);
-        uint64_t fp = cpd::io::graph_fingerprint(g.n, g.row_ptr.data(), g.dst.data(), g.w.data());
-        if (inputs.size() > 1) diff_cache[inputs[1]] = cpd::io::read_diff(inputs[1], g);
-        cpd_plan_opts o{};
-        o.no_hierarchy = 1;  // queries need the CSR + column order only
-        cli::check(cpd_plan_create(g.row_ptr.data(), g.dst.data(), g.w.data(), g.n, g.m, &o, &plan),
-                   "plan");
-        std::vector<uint32_t> order(g.n);
-        cli::check(cpd_plan_order(plan, order.data()), "order");
-        std::vector<uint32_t> stored = cpd::io::read_order(cpd::io::order_path(outdir, xy), fp);
-        if (stored != order) throw std::runtime_error("stored column order differs from this build's");
-        for (size_t k = 0; k < paths.size(); ++k) {
-            const bool rle = formats[k] == 1;
-            const uint64_t bfp = rle ? heads[k].fingerprint : mheads[k].fingerprint;
-            const uint32_t bkey = rle ? heads[k].key : mheads[k].key;
-            const uint32_t bmethod = rle ? heads[k].method : mheads[k].method;
-            if (bfp != fp || bkey != (uint32_t)key || bmethod != (uint32_t)mcode)
-                throw std::runtime_error(paths[k] + " was built for another graph/partition");
-        }
-        const double t_graph0 = now();
-        dev_thr.join();
-        const double t_devwait = now() - t_graph0;
-        if (dev_rc != CPD_OK) throw std::runtime_error("device: " + dev_err);
-        if (ndev == 0) throw std::runtime_error("no GPU visible (this build has no CPU path)");
-        cli::check(cpd_graph_create(plan, device, &dg), "graph upload");
-        // then the rows, streamed in pieces of <= kPiece words (a longer row
-        // alone): a dense index never holds the worker's runs in HBM or RAM
-        const std::string im = a.str("index", "auto");
-        const int imode = im == "rle" ? CPD_INDEX_RLE : im == "dense" ? CPD_INDEX_DENSE : CPD_INDEX_AUTO;
-        cli::check(cpd_index_create_empty(dg, targets.data(), (uint32_t)targets.size(), imode,
-                                          total_runs, &ix),
-                   "index");
-        const double t_rows0 = now();
-        constexpr uint64_t kPiece = 64ull << 20;  // 256 MB
-        std::vector<uint32_t> buf;
-        std::vector<uint64_t> rel;
-        // compact buckets: pieces read into two page-locked buffers by a
-        // reader thread while the previous piece is appended (uploaded)
-        uint32_t* pin[2] = {nullptr, nullptr};
-        uint64_t pin_bytes = 0;
-        const int read_threads = (int)a.num("read-threads", 8);
-        for (size_t k = 0; k < paths.size(); ++k) {
-            if (formats[k] == 2) {
-                const auto& mh = mheads[k];
-                const uint32_t nr = (uint32_t)mh.targets.size();
-                if (!nr) continue;
-                const uint32_t per = (uint32_t)std::min<uint64_t>(nr, std::max<uint64_t>(1, kPiece / mh.words));
-                if (4ull * mh.words * per > pin_bytes) {  // grown for this bucket's pieces
-                    for (auto& p : pin) {
-                        cpd_host_free(p);
-                        void* q = nullptr;
-                        cli::check(cpd_host_alloc(4ull * mh.words * per, &q), "pinned buffer");
-                        p = static_cast<uint32_t*>(q);
-                    }
-                    pin_bytes = 4ull * mh.words * per;
-                }
-                auto read = [&, k, per, nr](uint32_t r0, int slot) {
-                    cpd::io::read_move_bucket_rows(paths[k], mheads[k], r0, std::min(per, nr - r0), pin[slot],
-                                                   read_threads);
-                };
-                std::future<void> rd = std::async(std::launch::async, read, 0u, 0);
-                for (uint32_t r0 = 0, i = 0; r0 < nr; r0 += per, ++i) {
-                    rd.get();  // piece i is in pin[i & 1] (a read error is rethrown here)
-                    if (r0 + per < nr) rd = std::async(std::launch::async, read, r0 + per, (int)((i + 1) & 1u));
-                    const int rc = cpd_index_append_moves(ix, std::min(per, nr - r0), mh.bits, pin[i & 1u]);
-                    if (rc != CPD_OK) {
-                        if (rd.valid()) rd.wait();
-                        cli::check(rc, "index rows");
-                    }
-                }
-                continue;
-            }
-            const auto& off = heads[k].offsets;
-            const uint32_t nr = (uint32_t)heads[k].targets.size();
-            for (uint32_t r0 = 0; r0 < nr;) {
-                uint32_t r1 = r0 + 1;
-                while (r1 < nr && off[r1 + 1] - off[r0] <= kPiece) ++r1;
-                buf.resize(off[r1] - off[r0]);
-                cpd::io::read_bucket_runs(paths[k], heads[k], off[r0], buf.size(), buf.data());
-                rel.resize(r1 - r0 + 1);
-                for (uint32_t i = r0; i <= r1; ++i) rel[i - r0] = off[i] - off[r0];
-                cli::check(cpd_index_append_rows(ix, r1 - r0, rel.data(), buf.data()), "index rows");
-                r0 = r1;
-            }
-        }
-        for (auto p : pin) cpd_host_free(p);
-        const double t_rows = now() - t_rows0;
-        int mode = 0;
-        cli::check(cpd_index_get_mode(ix, &mode), "index mode");
-        // one machine-readable line (bench.py's full-build leg reads it)
-        std::printf("fifo_auto-json: {\"worker\": %lld, \"rows\": %zu, \"runs\": %llu, "
-                    "\"index\": \"%s\", \"compact_bytes\": %llu, \"read_plan_s\": %.3f, "
-                    "\"device_s\": %.3f, \"device_wait_s\": %.3f, \"arena\": %s, "
-                    "\"graph_s\": %.3f, \"rows_s\": %.3f, \"ready_s\": %.3f}\n",
-                    wid, targets.size(), (unsigned long long)total_runs,
-                    mode == CPD_INDEX_DENSE ? "dense" : "rle", (unsigned long long)compact_bytes,
-                    t_graph0 - t0, t_dev, t_devwait, arena ? "true" : "false",
-                    t_rows0 - t_graph0, t_rows, now() - t0);
-        std::printf("fifo_auto: worker %lld: %zu rows, %llu runs (%s index) on device %d, ready in "
-                    "%.3fs; listening on %s\n",
-                    wid, targets.size(), (unsigned long long)total_runs,
-                    mode == CPD_INDEX_DENSE ? "dense" : "rle", device, now() - t0, fifo.c_str());
-        std::fflush(stdout);
+        L = load(o);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "fifo_auto: %s\n", e.what());
-        ::unlink(fifo.c_str());
+        ::unlink(o.fifo.c_str());
         return 1;
     }
-
+    Server server{o, L};
     while (!g_stop) {
-        std::string msg = read_all(fifo);
+        const std::string msg = read_all(o.fifo);
         if (g_stop) break;
         if (msg.empty()) continue;
-        size_t nl = msg.find('\n');
-        std::string conf = msg.substr(0, nl);
-        if (conf == "quit" || conf == "exit") break;
-        std::string rest = nl == std::string::npos ? "" : msg.substr(nl + 1);
-        char qfile[4096] = {0}, answer[4096] = {0}, dname[4096] = {0};
-        int got = std::sscanf(rest.c_str(), "%4095s %4095s %4095s", qfile, answer, dname);
-        if (got < 2) {
-            std::fprintf(stderr, "fifo_auto: malformed request: %s\n", msg.c_str());
-            continue;
-        }
-        std::string diff = got >= 3 ? dname : "-";
-        int k_moves = -1;
-        std::string km = json_field(conf, "k_moves");
-        if (!km.empty()) k_moves = std::atoi(km.c_str());
-        bool debug = json_field(conf, "debug") == "true";
-        // cpd-search knobs (process_query.py:149-160): hscale, fscale, time
-        // (ns; args.get_time_ns may send a float), itrs; wall-clock time
-        // limit; the workspace (first-pass columns per lane, escalation,
-        // share of HBM) is the library's policy (capacity 0), the one the
-        // bench measures
-        cpd_search_opts so{1.0, 0.0, k_moves, -1, 0, 0, 0, CPD_SEARCH_AUTO, 0.0, 0};
-        if (!json_field(conf, "hscale").empty()) so.hscale = std::atof(json_field(conf, "hscale").c_str());
-        if (!json_field(conf, "fscale").empty()) so.fscale = std::atof(json_field(conf, "fscale").c_str());
-        if (!json_field(conf, "itrs").empty()) so.itrs = std::atoll(json_field(conf, "itrs").c_str());
-        if (!json_field(conf, "time").empty()) {
-            const double tn = std::atof(json_field(conf, "time").c_str());
-            so.time_ns = tn > 0 ? (uint64_t)tn : 0;
-        }
-        std::string line = "0,0,0,0,0,0,0,0,0,0";
-        try {
-            double t0 = now();
-            // kept across requests: their pages stay mapped
-            static std::vector<uint32_t> s, t;
-            cpd::io::read_query_file(qfile, parse_threads, s, t);
-            static std::vector<uint64_t> dep;
-            if (timed) read_departures(qfile, s.size(), dep);
-            const double t_read = now() - t0;
-            if (costs || timed) {
-                // the diff field is a list: its sets, loaded beside (and
-                // independent of) the index's current weights
-                if (diff != active_sets) {
-                    std::vector<const uint32_t*> sets;
-                    for (size_t p0 = 0; p0 <= diff.size();) {
-                        size_t p1 = diff.find(',', p0);
-                        if (p1 == std::string::npos) p1 = diff.size();
-                        const std::string name = diff.substr(p0, p1 - p0);
-                        if (name.empty()) throw std::runtime_error("empty name in diff list '" + diff + "'");
-                        if (sets.size() == CPD_MAX_WEIGHT_SETS)
-                            throw std::runtime_error("more than " + std::to_string(CPD_MAX_WEIGHT_SETS) +
-                                                     " diffs in '" + diff + "'");
-                        if (name == "-") {
-                            sets.push_back(nullptr);
-                        } else {
-                            auto it = diff_cache.find(name);
-                            if (it == diff_cache.end())
-                                it = diff_cache.emplace(name, cpd::io::read_diff(name, g)).first;
-                            sets.push_back(it->second.data());
-                        }
-                        p0 = p1 + 1;
-                    }
-                    active_sets.clear();
-                    if (cpd_index_set_weight_sets(ix, (uint32_t)sets.size(), sets.data()) != CPD_OK)
-                        throw std::runtime_error(cpd_last_error());
-                    active_sets = diff;
-                    active_nsets = sets.size();
-                }
-            } else if (diff != active_diff) {
-                if (diff == "-" ) {
-                    cli::check(cpd_index_set_weights(ix, nullptr), "weights");
-                } else {
-                    auto it = diff_cache.find(diff);
-                    if (it == diff_cache.end())
-                        it = diff_cache.emplace(diff, cpd::io::read_diff(diff, g)).first;
-                    cli::check(cpd_index_set_weights(ix, it->second.data()), "weights");
-                }
-                active_diff = diff;
-            }
-            const size_t nq = s.size();
-            int rc = cpd_query_prepare(ix, s.data(), t.data(), (uint32_t)nq);
-            if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-            double t_receive = now() - t0;
-            cpd_query_stats st{};
-            cpd_search_stats ss{};
-            if (assign) {
-                // the loop leaves w_{K+1} on the index: the next request sets
-                // its diff's weights again, whatever its name
-                active_diff.clear();
-                static std::vector<uint32_t> cap;
-                cap.assign(g.m, (uint32_t)assign_cap);
-                const uint32_t iters = (uint32_t)assign_iters;
-                std::vector<std::string> lines;
-                const double search_ms =
-                    step_line   ? run_assign<cpd_assign_line_iter>(cpd_query_assign_line, ix, so, cap,
-                                                                   vdf, iters, lines)
-                    : step_conj ? run_assign<cpd_assign_conj_iter>(cpd_query_assign_conj, ix, so, cap,
-                                                                   vdf, iters, lines)
-                                : run_assign<cpd_assign_iter>(assign_msa, ix, so, cap, vdf, iters, lines);
-                if (step_line || step_conj) write_flow(ix, qfile, g);
-                else write_loads(ix, qfile, g, 1);
-                write_assign(ix, qfile, g, lines);
-                // the answer line's sums, from the last iteration's search
-                std::vector<uint32_t> cnt(5 * nq), plen(nq);
-                std::vector<uint8_t> fin(nq);
-                if (nq) cli::check(cpd_query_search_counters(ix, cnt.data()), "counters");
-                cli::check(cpd_query_fetch(ix, nullptr, plen.data(), fin.data()), "fetch");
-                uint64_t* sums[5] = {&ss.expanded, &ss.inserted, &ss.touched, &ss.updated, &ss.surplus};
-                for (size_t q = 0; q < nq; ++q) {
-                    for (int k = 0; k < 5; ++k) *sums[k] += cnt[5 * q + k];
-                    if (fin[q] == 1) {
-                        ss.plen += plen[q];
-                        ss.finished++;
-                    } else if (fin[q] == 2) {
-                        ss.overflow++;
-                    }
-                }
-                ss.tables_ms = 0.0;
-                ss.kernel_ms = search_ms;  // tables included
-                if (ss.overflow)
-                    std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
-                                 (unsigned long long)ss.overflow);
-            } else if (search) {
-                static std::vector<uint64_t> spoff;
-                if (search_paths) {
-                    spoff.resize(nq + 1);
-                    rc = cpd_query_search_paths(ix, &so, 0, spoff.data(), &ss, nullptr);
-                } else if (search_loads) {
-                    rc = cpd_query_search_loads(ix, &so, 0, nullptr, 0, &ss, nullptr);
-                } else {
-                    rc = cpd_query_search(ix, &so, &ss);
-                }
-                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                if (search_paths) write_paths(ix, qfile, s, t, spoff);
-                if (search_loads) write_loads(ix, qfile, g, 1);
-                if (ss.overflow)
-                    std::fprintf(stderr, "fifo_auto: %llu searches exceeded the workspace and stopped unfinished\n",
-                                 (unsigned long long)ss.overflow);
-            } else if (costs) {
-                rc = cpd_query_costs(ix, k_moves, (uint32_t)slice_moves, &st);
-                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                write_costs(ix, qfile, s, t, slice_moves ? 1u : active_nsets);
-            } else if (timed) {
-                rc = cpd_query_timed(ix, k_moves, dep.empty() ? nullptr : dep.data(),
-                                     (uint64_t)period, nullptr, loads ? CPD_TIMED_LOADS : 0u, &st);
-                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                write_timed(ix, qfile, s, t, dep);
-                if (loads) write_loads(ix, qfile, g, active_nsets);
-            } else if (loads) {
-                rc = cpd_query_loads(ix, k_moves, nullptr, (uint32_t)load_slices,
-                                     (uint32_t)load_slice_moves, 0, &st);
-                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                write_loads(ix, qfile, g, (size_t)load_slices);
-            } else if (paths) {
-                static std::vector<uint64_t> poff;
-                poff.resize(nq + 1);
-                rc = cpd_query_paths(ix, k_moves, poff.data(), &st);
-                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-                write_paths(ix, qfile, s, t, poff);
-            } else {
-                rc = cpd_query_run(ix, k_moves, &st);
-                if (rc != CPD_OK) throw std::runtime_error(cpd_last_error());
-            }
-            if (debug && !costs && !timed) {
-                std::vector<uint64_t> cost(nq);
-                std::vector<uint32_t> hops(nq);
-                std::vector<uint8_t> fin(nq);
-                cli::check(cpd_query_fetch(ix, cost.data(), hops.data(), fin.data()), "fetch");
-                std::string res = std::string(qfile) + ".res";
-                if (std::FILE* f = std::fopen(res.c_str(), "w")) {
-                    for (size_t i = 0; i < nq; ++i)
-                        std::fprintf(f, "%u %u %llu %u %u\n", s[i], t[i], (unsigned long long)cost[i],
-                                     hops[i], fin[i] == 1 ? 1u : 0u);
-                    std::fclose(f);
-                }
-            }
-            // t_receive = query file read + parse + upload and sort on the
-            // GPU; t_search = the algorithm's device time (table-search: the
-            // walk kernel; cpd-search: the search passes + any table rebuild
-            // for new weights), the same meaning for both; t_astar = the A*
-            // passes alone (0 for table-search)
-            char buf[512];
-            if (search)
-                std::snprintf(buf, sizeof buf, "%llu,%llu,%llu,%llu,%llu,%llu,%llu,%lld,%lld,%lld",
-                              (unsigned long long)ss.expanded, (unsigned long long)ss.inserted,
-                              (unsigned long long)ss.touched, (unsigned long long)ss.updated,
-                              (unsigned long long)ss.surplus, (unsigned long long)ss.plen,
-                              (unsigned long long)ss.finished, (long long)(t_receive * 1e9),
-                              (long long)(ss.kernel_ms * 1e6),
-                              (long long)((ss.kernel_ms + ss.tables_ms) * 1e6));
-            else
-                std::snprintf(buf, sizeof buf, "%llu,0,0,0,0,%llu,%llu,%lld,0,%lld",
-                              (unsigned long long)st.hops, (unsigned long long)st.hops,
-                              (unsigned long long)st.finished, (long long)(t_receive * 1e9),
-                              (long long)(st.kernel_ms * 1e6));
-            line = buf;
-            if (verbose)  // the receive phase split (stderr: nothing reads stdout by then)
-                std::fprintf(stderr, "fifo_auto-req: {\"queries\": %zu, \"read_parse_s\": %.6f, "
-                             "\"prepare_s\": %.6f, \"compute_s\": %.6f}\n", nq, t_read,
-                             t_receive - t_read, search ? ss.kernel_ms * 1e-3 : st.kernel_ms * 1e-3);
-        } catch (const std::exception& e) {
-            std::fprintf(stderr, "fifo_auto: request failed: %s\n", e.what());
-        }
-        if (!write_answer(answer, line))
-            std::fprintf(stderr, "fifo_auto: cannot write answer to %s\n", answer);
-        if (once) break;
+        const std::string first = msg.substr(0, msg.find('\n'));
+        if (first == "quit" || first == "exit") break;
+        Request r;
+        if (!parse_request(msg, r)) continue;
+        const std::string line = server.answer(r);
+        if (!write_answer(r.answer, line))
+            std::fprintf(stderr, "fifo_auto: cannot write answer to %s\n", r.answer.c_str());
+        if (o.once) break;
     }
-    cpd_index_free(ix);
-    cpd_graph_free(dg);
-    cpd_plan_free(plan);
-    if (arena) cpd_device_arena_release(device);
+    unload(L);
     return 0;
 }
+

@@ -136,6 +136,66 @@ def run(conf, config=None, script_dir=None):
     return parts, stats
 
 
+def build_index(tmp_path, W, method, key, width=30, height=24, seed=2, queries=1500):
+    """A gen_synth graph with its diff and scenario under tmp_path, and its CPD
+    built by W make_cpd_auto workers; returns xy, diff, scen, outdir."""
+    prefix = str(tmp_path / "g")
+    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", str(width), "--height",
+                    str(height), "--seed", str(seed), "--out", prefix, "--queries", str(queries)],
+                   check=True, capture_output=True)
+    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
+    outdir = str(tmp_path / "index")
+    for wid in range(W):
+        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
+                            method, "--partkey", str(key), "--workerid", str(wid), "--maxworker",
+                            str(W), "--outdir", outdir, "--device", "0"],
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr
+    return xy, diff, scen, outdir
+
+
+def serve(xy, diff, outdir, alg, extra, W, method, key):
+    """W resident fifo_auto workers on /tmp/worker{wid}.fifo, all on device 0."""
+    procs = []
+    for wid in range(W):
+        fifo = f"/tmp/worker{wid}.fifo"
+        if os.path.exists(fifo):
+            os.remove(fifo)
+        procs.append(subprocess.Popen(
+            [os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod", method,
+             "--partkey", str(key), "--workerid", str(wid), "--maxworker", str(W), "--outdir",
+             outdir, "--alg", alg, "--device", "0"] + extra,
+            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    return procs
+
+
+def quit(procs):
+    """Ends the workers serve() started and removes their FIFOs."""
+    for wid, pr in enumerate(procs):
+        fifo = f"/tmp/worker{wid}.fifo"
+        if pr.poll() is None:
+            try:
+                with open(fifo, "w") as f:
+                    f.write("quit\n")
+                pr.wait(timeout=20)
+            except Exception:
+                pr.kill()
+        if os.path.exists(fifo):
+            os.remove(fifo)
+
+
+def refused(xy, diff, outdir, extra, tmp_path, W, method, key):
+    """Worker 0 started with a flag combination it refuses: one line on stderr
+    and no FIFO made; returns the completed process for the caller's checks."""
+    p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod",
+                        method, "--partkey", str(key), "--workerid", "0", "--maxworker", str(W),
+                        "--outdir", outdir, "--fifo", str(tmp_path / "never.fifo")] + extra,
+                       capture_output=True, text=True, timeout=60)
+    assert len(p.stderr.strip().splitlines()) == 1
+    assert not os.path.exists(tmp_path / "never.fifo")
+    return p
+
+
 def wait_ready(proc, timeout=60):
     """Block until a resident fifo_auto prints its "listening" line; returns
     its stdout so far.  Reads the raw pipe (os.read after select): a buffered

@@ -6,7 +6,6 @@ cpd_query_assign at a demand of 1 per query line and a uniform capacity;
 process, <query file>.diff reads back to its final weights, and the flag
 combinations the loop cannot serve are refused at start."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,25 +14,15 @@ import cpd
 import driver_harness as H
 import oracle
 from test_gpu_drivers import _read_diff
-from test_gpu_search_paths_driver import KEY, METHOD, W, _quit, _serve
 
 pytestmark = pytest.mark.gpu
 BIN = H.BIN
+W, METHOD, KEY = 2, "mod", 3
 ITERS, CAP = 3, 2
 
 
 def test_fifo_auto_assign(tmp_path):
-    prefix = str(tmp_path / "g")
-    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "30", "--height", "24", "--seed",
-                    "2", "--out", prefix, "--queries", "1500"], check=True, capture_output=True)
-    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
-    outdir = str(tmp_path / "index")
-    for wid in range(W):
-        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", str(wid), "--maxworker",
-                            str(W), "--outdir", outdir, "--device", "0"],
-                           capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stderr
+    xy, diff, scen, outdir = H.build_index(tmp_path, W, METHOD, KEY)
     g = cpd.synth_road_graph(30, 24, seed=2)
     wc = _read_diff(diff, g)
     src = np.repeat(np.arange(g.n), np.diff(g.row_ptr.astype(np.int64)))
@@ -49,17 +38,14 @@ def test_fifo_auto_assign(tmp_path):
                   ["--alg", "cpd-search", "--assign", "0", "--capacity", "2"],
                   ["--alg", "cpd-search", "--capacity", "2"],                 # no --assign
                   ["--alg", "cpd-search", "--vdf", "3/20^5"] + loop):
-        p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", "0", "--maxworker", str(W),
-                            "--outdir", outdir, "--fifo", str(tmp_path / "never.fifo")] + extra,
-                           capture_output=True, text=True, timeout=60)
+        p = H.refused(xy, diff, outdir, extra, tmp_path, W, METHOD, KEY)
         assert p.returncode == 2, (extra, p.stderr)
         assert len(p.stderr.strip().splitlines()) == 1 and "fifo_auto: --" in p.stderr, extra
         assert not os.path.exists(tmp_path / "never.fifo")
 
     nfs = str(tmp_path / "nfs")
     os.makedirs(nfs)
-    procs = _serve(xy, diff, outdir, loop)
+    procs = H.serve(xy, diff, outdir, "cpd-search", loop, W, METHOD, KEY)
     try:
         for pr in procs:
             H.wait_ready(pr, timeout=60)
@@ -67,7 +53,7 @@ def test_fifo_auto_assign(tmp_path):
                 "xy_file": xy, "scenfile": scen, "diffs": [diff, diff]}  # the request twice
         parts, stats = H.run(conf, dict(H.DEFAULT_CONFIG, debug=True))
     finally:
-        _quit(procs)
+        H.quit(procs)
     side = sorted(f for f in os.listdir(nfs) if f.startswith("query."))
     assert side == sorted(f"query.localhost{wid}.{ext}" for wid in range(W)
                           for ext in ("assign", "diff", "loads", "res"))  # no .tmp left

@@ -4,47 +4,35 @@ test_gpu_flow_driver.py does): every request is answered through
 cpd_query_assign_conj; <query file>.assign, .loads and .diff equal what
 tests/conj_ref.py computes under the request's diff."""
 import os
-import subprocess
 
 import numpy as np
 
 import pytest
 
 import cpd
+import driver_harness as H
 import oracle
 from assign_ref import BPR
 from conj_ref import ref_assign_conj
 from search_paths_ref import SearchPathsRef
 from test_gpu_drivers import _read_diff
 from test_gpu_flow_driver import BIN, CAP, _round
-from test_gpu_search_paths_driver import KEY, METHOD, W
 
 pytestmark = pytest.mark.gpu
+W, METHOD, KEY = 2, "mod", 3
 ITERS = 4
 
 
 def test_fifo_auto_assign_conj(tmp_path):
-    prefix = str(tmp_path / "g")
-    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "30", "--height", "24", "--seed",
-                    "2", "--out", prefix, "--queries", "600"], check=True, capture_output=True)
-    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
-    outdir = str(tmp_path / "index")
-    for wid in range(W):
-        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", str(wid), "--maxworker",
-                            str(W), "--outdir", outdir, "--device", "0"],
-                           capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stderr
+    xy, diff, scen, outdir = H.build_index(tmp_path, W, METHOD, KEY, queries=600)
     g = cpd.synth_road_graph(30, 24, seed=2)
     wc = _read_diff(diff, g)
     src = np.repeat(np.arange(g.n), np.diff(g.row_ptr.astype(np.int64)))
     order = oracle.dfs_preorder(g.row_ptr, g.dst)
 
     # --step conj without --assign is refused as the other words are
-    p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod",
-                        METHOD, "--partkey", str(KEY), "--workerid", "0", "--maxworker", str(W),
-                        "--outdir", outdir, "--fifo", str(tmp_path / "never.fifo"), "--alg",
-                        "cpd-search", "--step", "conj"], capture_output=True, text=True, timeout=60)
+    p = H.refused(xy, diff, outdir, ["--alg", "cpd-search", "--step", "conj"], tmp_path, W, METHOD,
+                  KEY)
     assert p.returncode == 2 and p.stderr.startswith("fifo_auto: --step")
     assert len(p.stderr.strip().splitlines()) == 1 and not os.path.exists(tmp_path / "never.fifo")
 

@@ -4,7 +4,6 @@ a list of diffs, the walk runs once, <query file>.res holds every query's cost
 under each diff (or, with --slice-moves, the one sliced cost) equal to the
 oracle's, and the answer line is the one a run without the flag gives."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,10 +12,10 @@ import costs_ref as R
 import cpd
 import driver_harness as H
 import oracle
-from test_gpu_paths_driver import METHOD, KEY, W, _quit, _serve
 
 pytestmark = pytest.mark.gpu
 BIN = H.BIN
+W, METHOD, KEY = 2, "mod", 3
 
 
 def write_diff(path, g, wc):
@@ -36,17 +35,7 @@ def write_diff(path, g, wc):
 
 
 def test_fifo_auto_costs(tmp_path):
-    prefix = str(tmp_path / "g")
-    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "30", "--height", "24", "--seed",
-                    "2", "--out", prefix, "--queries", "1500"], check=True, capture_output=True)
-    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
-    outdir = str(tmp_path / "index")
-    for wid in range(W):
-        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", str(wid), "--maxworker",
-                            str(W), "--outdir", outdir, "--device", "0"],
-                           capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stderr
+    xy, diff, scen, outdir = H.build_index(tmp_path, W, METHOD, KEY)
     g = cpd.synth_road_graph(30, 24, seed=2)
     order = oracle.dfs_preorder(g.row_ptr, g.dst)
     da, db = str(tmp_path / "a.diff"), str(tmp_path / "b.diff")
@@ -58,10 +47,7 @@ def test_fifo_auto_costs(tmp_path):
     # --costs is table-search's, and not --paths': refused at start, with one line
     for extra in (["--alg", "cpd-search", "--costs"], ["--alg", "table-search", "--paths", "--costs"],
                   ["--alg", "table-search", "--slice-moves", "4"]):
-        p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", "0", "--maxworker", str(W),
-                            "--outdir", outdir, "--fifo", str(tmp_path / "never.fifo")] + extra,
-                           capture_output=True, text=True, timeout=60)
+        p = H.refused(xy, diff, outdir, extra, tmp_path, W, METHOD, KEY)
         assert p.returncode != 0
         assert len(p.stderr.strip().splitlines()) == 1
         assert ("--costs" in p.stderr) and not os.path.exists(tmp_path / "never.fifo")
@@ -71,7 +57,7 @@ def test_fifo_auto_costs(tmp_path):
                            ("sliced", ["--costs", "--slice-moves", "4"], 4)):
         nfs = str(tmp_path / f"nfs_{name}")
         os.makedirs(nfs)
-        procs = _serve(xy, diff, outdir, extra)
+        procs = H.serve(xy, diff, outdir, "table-search", extra, W, METHOD, KEY)
         try:
             for pr in procs:
                 H.wait_ready(pr, timeout=60)
@@ -80,7 +66,7 @@ def test_fifo_auto_costs(tmp_path):
                     "diffs": ["-" if S is None else f"-,{da},{db}"]}
             parts, stats = H.run(conf, dict(H.DEFAULT_CONFIG))
         finally:
-            _quit(procs)
+            H.quit(procs)
         answers[name] = stats[0]
         side = sorted(f for f in os.listdir(nfs) if f.endswith(".res"))
         if S is None:

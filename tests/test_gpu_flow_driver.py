@@ -5,7 +5,6 @@ cpd_query_assign_line; <query file>.assign, .loads and .diff equal what
 tests/flow_ref.py computes under the request's diff, and --step msa writes
 byte for byte what a run without --step writes."""
 import os
-import subprocess
 
 import numpy as np
 
@@ -18,10 +17,10 @@ from assign_ref import BPR
 from flow_ref import ref_assign_line
 from search_paths_ref import SearchPathsRef
 from test_gpu_drivers import _read_diff
-from test_gpu_search_paths_driver import KEY, METHOD, W, _quit, _serve
 
 pytestmark = pytest.mark.gpu
 BIN = H.BIN
+W, METHOD, KEY = 2, "mod", 3
 ITERS, CAP = 3, 2
 EXTS = ("assign", "diff", "loads", "res")
 
@@ -30,7 +29,7 @@ def _round(tmp_path, name, xy, diff, scen, outdir, extra):
     """One serving session answering one request; returns (nfs dir, parts)."""
     nfs = str(tmp_path / name)
     os.makedirs(nfs)
-    procs = _serve(xy, diff, outdir, extra)
+    procs = H.serve(xy, diff, outdir, "cpd-search", extra, W, METHOD, KEY)
     try:
         for pr in procs:
             H.wait_ready(pr, timeout=60)
@@ -38,24 +37,14 @@ def _round(tmp_path, name, xy, diff, scen, outdir, extra):
                 "xy_file": xy, "scenfile": scen, "diffs": [diff]}
         parts, _ = H.run(conf, dict(H.DEFAULT_CONFIG, debug=True))
     finally:
-        _quit(procs)
+        H.quit(procs)
     side = sorted(f for f in os.listdir(nfs) if f.startswith("query."))
     assert side == sorted(f"query.localhost{wid}.{ext}" for wid in range(W) for ext in EXTS)
     return nfs, parts
 
 
 def test_fifo_auto_assign_line(tmp_path):
-    prefix = str(tmp_path / "g")
-    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "30", "--height", "24", "--seed",
-                    "2", "--out", prefix, "--queries", "600"], check=True, capture_output=True)
-    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
-    outdir = str(tmp_path / "index")
-    for wid in range(W):
-        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", str(wid), "--maxworker",
-                            str(W), "--outdir", outdir, "--device", "0"],
-                           capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stderr
+    xy, diff, scen, outdir = H.build_index(tmp_path, W, METHOD, KEY, queries=600)
     g = cpd.synth_road_graph(30, 24, seed=2)
     wc = _read_diff(diff, g)
     src = np.repeat(np.arange(g.n), np.diff(g.row_ptr.astype(np.int64)))
@@ -66,10 +55,7 @@ def test_fifo_auto_assign_line(tmp_path):
     for extra in (["--alg", "cpd-search", "--step", "line"],                  # no --assign
                   ["--alg", "cpd-search", "--step", "msa"],
                   ["--alg", "cpd-search", "--step", "fw"] + loop):
-        p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", "0", "--maxworker", str(W),
-                            "--outdir", outdir, "--fifo", str(tmp_path / "never.fifo")] + extra,
-                           capture_output=True, text=True, timeout=60)
+        p = H.refused(xy, diff, outdir, extra, tmp_path, W, METHOD, KEY)
         assert p.returncode == 2, (extra, p.stderr)
         assert len(p.stderr.strip().splitlines()) == 1 and "fifo_auto: --step" in p.stderr, extra
         assert not os.path.exists(tmp_path / "never.fifo")

@@ -5,7 +5,6 @@ file>.loads holds every loaded edge's load (or, with --load-slices /
 --load-slice-moves, its load per time slice) equal to the reference's, and the
 answer line is the one a run without the flag gives."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,24 +13,14 @@ import cpd
 import driver_harness as H
 import loads_ref as L
 import oracle
-from test_gpu_paths_driver import METHOD, KEY, W, _quit, _serve
 
 pytestmark = pytest.mark.gpu
 BIN = H.BIN
+W, METHOD, KEY = 2, "mod", 3
 
 
 def test_fifo_auto_loads(tmp_path):
-    prefix = str(tmp_path / "g")
-    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "30", "--height", "24", "--seed",
-                    "2", "--out", prefix, "--queries", "1500"], check=True, capture_output=True)
-    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
-    outdir = str(tmp_path / "index")
-    for wid in range(W):
-        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", str(wid), "--maxworker",
-                            str(W), "--outdir", outdir, "--device", "0"],
-                           capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stderr
+    xy, diff, scen, outdir = H.build_index(tmp_path, W, METHOD, KEY)
     g = cpd.synth_road_graph(30, 24, seed=2)
     order = oracle.dfs_preorder(g.row_ptr, g.dst)
     src = np.repeat(np.arange(g.n), np.diff(g.row_ptr.astype(np.int64)))
@@ -39,10 +28,7 @@ def test_fifo_auto_loads(tmp_path):
     # --loads is table-search's, and not --paths' or --costs': refused at start, with one line
     for extra in (["--alg", "cpd-search", "--loads"], ["--alg", "table-search", "--paths", "--loads"],
                   ["--alg", "table-search", "--costs", "--loads"]):
-        p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", "0", "--maxworker", str(W),
-                            "--outdir", outdir, "--fifo", str(tmp_path / "never.fifo")] + extra,
-                           capture_output=True, text=True, timeout=60)
+        p = H.refused(xy, diff, outdir, extra, tmp_path, W, METHOD, KEY)
         assert p.returncode != 0
         assert len(p.stderr.strip().splitlines()) == 1
         assert ("--loads" in p.stderr) and not os.path.exists(tmp_path / "never.fifo")
@@ -53,7 +39,7 @@ def test_fifo_auto_loads(tmp_path):
                                           "4"], 3, 4)):
         nfs = str(tmp_path / f"nfs_{name}")
         os.makedirs(nfs)
-        procs = _serve(xy, diff, outdir, extra)
+        procs = H.serve(xy, diff, outdir, "table-search", extra, W, METHOD, KEY)
         try:
             for pr in procs:
                 H.wait_ready(pr, timeout=60)
@@ -61,7 +47,7 @@ def test_fifo_auto_loads(tmp_path):
                     "xy_file": xy, "scenfile": scen, "diffs": ["-"]}
             parts, stats = H.run(conf, dict(H.DEFAULT_CONFIG))
         finally:
-            _quit(procs)
+            H.quit(procs)
         answers[name] = stats[0]
         side = sorted(os.listdir(nfs))
         if K is None:

@@ -3,7 +3,6 @@
 one a run without the flag gives, and <query file>.paths holds every walk's
 nodes, equal to the numpy walk of test_gpu_paths.py over the oracle's rows."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,54 +17,14 @@ BIN = H.BIN
 W, METHOD, KEY = 2, "mod", 3
 
 
-def _serve(xy, diff, outdir, extra):
-    procs = []
-    for wid in range(W):
-        fifo = f"/tmp/worker{wid}.fifo"
-        if os.path.exists(fifo):
-            os.remove(fifo)
-        procs.append(subprocess.Popen(
-            [os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod", METHOD,
-             "--partkey", str(KEY), "--workerid", str(wid), "--maxworker", str(W), "--outdir",
-             outdir, "--alg", "table-search", "--device", "0"] + extra,
-            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    return procs
-
-
-def _quit(procs):
-    for wid, pr in enumerate(procs):
-        fifo = f"/tmp/worker{wid}.fifo"
-        if pr.poll() is None:
-            try:
-                with open(fifo, "w") as f:
-                    f.write("quit\n")
-                pr.wait(timeout=20)
-            except Exception:
-                pr.kill()
-        if os.path.exists(fifo):
-            os.remove(fifo)
-
 
 def test_fifo_auto_paths(tmp_path):
-    prefix = str(tmp_path / "g")
-    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "30", "--height", "24", "--seed",
-                    "2", "--out", prefix, "--queries", "1500"], check=True, capture_output=True)
-    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
-    outdir = str(tmp_path / "index")
-    for wid in range(W):
-        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", str(wid), "--maxworker",
-                            str(W), "--outdir", outdir, "--device", "0"],
-                           capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stderr
+    xy, diff, scen, outdir = H.build_index(tmp_path, W, METHOD, KEY)
     g = cpd.synth_road_graph(30, 24, seed=2)
     order = oracle.dfs_preorder(g.row_ptr, g.dst)
 
     # cpd-search has no paths: refused at start, with one line
-    p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod", METHOD,
-                        "--partkey", str(KEY), "--workerid", "0", "--maxworker", str(W), "--outdir",
-                        outdir, "--alg", "cpd-search", "--paths", "--fifo",
-                        str(tmp_path / "never.fifo")], capture_output=True, text=True, timeout=60)
+    p = H.refused(xy, diff, outdir, ["--alg", "cpd-search", "--paths"], tmp_path, W, METHOD, KEY)
     assert p.returncode != 0
     assert len(p.stderr.strip().splitlines()) == 1 and "--paths" in p.stderr
     assert not os.path.exists(tmp_path / "never.fifo")
@@ -74,7 +33,8 @@ def test_fifo_auto_paths(tmp_path):
     for flag in (False, True):
         nfs = str(tmp_path / ("nfs_paths" if flag else "nfs_plain"))
         os.makedirs(nfs)
-        procs = _serve(xy, diff, outdir, ["--paths"] if flag else [])
+        procs = H.serve(xy, diff, outdir, "table-search", ["--paths"] if flag else [], W, METHOD,
+                        KEY)
         try:
             for pr in procs:
                 H.wait_ready(pr, timeout=60)
@@ -82,7 +42,7 @@ def test_fifo_auto_paths(tmp_path):
                     "xy_file": xy, "scenfile": scen, "diffs": ["-"]}
             parts, stats = H.run(conf, dict(H.DEFAULT_CONFIG))
         finally:
-            _quit(procs)
+            H.quit(procs)
         answers[flag] = stats[0]
         side = sorted(f for f in os.listdir(nfs) if ".paths" in f)
         if not flag:

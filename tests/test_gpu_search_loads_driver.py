@@ -6,7 +6,6 @@ holds every loaded edge of the routes found under the request's diff, equal to
 ref_search_loads (tests/search_loads_ref.py) line for line, and the answer line
 and <query file>.res are those of a run without the flag."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,24 +16,14 @@ import oracle
 from search_loads_ref import ref_search_loads
 from search_paths_ref import SearchPathsRef
 from test_gpu_drivers import _read_diff
-from test_gpu_search_paths_driver import KEY, METHOD, W, _quit, _serve
 
 pytestmark = pytest.mark.gpu
 BIN = H.BIN
+W, METHOD, KEY = 2, "mod", 3
 
 
 def test_fifo_auto_search_loads(tmp_path):
-    prefix = str(tmp_path / "g")
-    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "30", "--height", "24", "--seed",
-                    "2", "--out", prefix, "--queries", "1500"], check=True, capture_output=True)
-    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
-    outdir = str(tmp_path / "index")
-    for wid in range(W):
-        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", str(wid), "--maxworker",
-                            str(W), "--outdir", outdir, "--device", "0"],
-                           capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stderr
+    xy, diff, scen, outdir = H.build_index(tmp_path, W, METHOD, KEY)
     g = cpd.synth_road_graph(30, 24, seed=2)
     order = oracle.dfs_preorder(g.row_ptr, g.dst)
     wc = _read_diff(diff, g)
@@ -46,10 +35,7 @@ def test_fifo_auto_search_loads(tmp_path):
                   ["--alg", "cpd-search", "--search-paths", "--search-loads"],
                   ["--alg", "cpd-search", "--search-loads", "--load-slices", "3",
                    "--load-slice-moves", "4"]):
-        p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", "0", "--maxworker", str(W),
-                            "--outdir", outdir, "--fifo", str(tmp_path / "never.fifo")] + extra,
-                           capture_output=True, text=True, timeout=60)
+        p = H.refused(xy, diff, outdir, extra, tmp_path, W, METHOD, KEY)
         assert p.returncode == 2, (extra, p.stderr)
         assert len(p.stderr.strip().splitlines()) == 1 and "--search-loads" in p.stderr
         assert not os.path.exists(tmp_path / "never.fifo")
@@ -59,7 +45,8 @@ def test_fifo_auto_search_loads(tmp_path):
     for flag in (False, True):
         nfs = str(tmp_path / ("nfs_loads" if flag else "nfs_plain"))
         os.makedirs(nfs)
-        procs = _serve(xy, diff, outdir, ["--search-loads"] if flag else [])
+        procs = H.serve(xy, diff, outdir, "cpd-search", ["--search-loads"] if flag else [], W,
+                        METHOD, KEY)
         try:
             for pr in procs:
                 H.wait_ready(pr, timeout=60)
@@ -67,7 +54,7 @@ def test_fifo_auto_search_loads(tmp_path):
                     "xy_file": xy, "scenfile": scen, "diffs": [diff]}
             parts, stats = H.run(conf, dict(config))
         finally:
-            _quit(procs)
+            H.quit(procs)
         answers[flag] = stats[0]
         res[flag] = [open(os.path.join(nfs, f"query.localhost{wid}.res")).read()
                      for wid in range(W)]

@@ -6,7 +6,6 @@ equal to tests/timed_ref.py's; with --loads <query file>.loads holds every
 loaded edge's load per diff.  A .dep that does not fit the query file fails the
 request, and the flag combinations that make no sense are refused at start."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,24 +15,14 @@ import driver_harness as H
 import oracle
 import timed_ref as T
 from test_gpu_costs_driver import write_diff
-from test_gpu_paths_driver import METHOD, KEY, W, _quit, _serve
 
 pytestmark = pytest.mark.gpu
 BIN = H.BIN
+W, METHOD, KEY = 2, "mod", 3
 
 
 def test_fifo_auto_timed(tmp_path):
-    prefix = str(tmp_path / "g")
-    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "30", "--height", "24", "--seed",
-                    "2", "--out", prefix, "--queries", "1500"], check=True, capture_output=True)
-    xy, diff, scen = prefix + ".xy", prefix + ".xy.diff", prefix + ".scen"
-    outdir = str(tmp_path / "index")
-    for wid in range(W):
-        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", xy, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", str(wid), "--maxworker",
-                            str(W), "--outdir", outdir, "--device", "0"],
-                           capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, p.stderr
+    xy, diff, scen, outdir = H.build_index(tmp_path, W, METHOD, KEY)
     g = cpd.synth_road_graph(30, 24, seed=2)
     order = oracle.dfs_preorder(g.row_ptr, g.dst)
     src = np.repeat(np.arange(g.n), np.diff(g.row_ptr.astype(np.int64)))
@@ -50,10 +39,7 @@ def test_fifo_auto_timed(tmp_path):
                   ["--alg", "table-search", "--timed", "100", "--load-slice-moves", "3"],
                   ["--alg", "table-search", "--timed", "0"],
                   ["--alg", "table-search", "--timed", str((1 << 60) + 1)]):
-        p = subprocess.run([os.path.join(BIN, "fifo_auto"), "--input", xy, diff, "--partmethod",
-                            METHOD, "--partkey", str(KEY), "--workerid", "0", "--maxworker", str(W),
-                            "--outdir", outdir, "--fifo", str(tmp_path / "never.fifo")] + extra,
-                           capture_output=True, text=True, timeout=60)
+        p = H.refused(xy, diff, outdir, extra, tmp_path, W, METHOD, KEY)
         assert p.returncode != 0
         assert len(p.stderr.strip().splitlines()) == 1
         assert ("--timed" in p.stderr) and not os.path.exists(tmp_path / "never.fifo")
@@ -92,7 +78,7 @@ def test_fifo_auto_timed(tmp_path):
 
     good = ["".join(f"{int(d)}\n" for d in dep) for dep in deps]
     for name, extra in (("timed", ["--timed", str(P)]), ("loads", ["--timed", str(P), "--loads"])):
-        procs = _serve(xy, diff, outdir, extra)
+        procs = H.serve(xy, diff, outdir, "table-search", extra, W, METHOD, KEY)
         try:
             for pr in procs:
                 H.wait_ready(pr, timeout=60)
@@ -106,7 +92,7 @@ def test_fifo_auto_timed(tmp_path):
                 mal = [good[0].replace("\n", "x\n", 1)] + [text + "7\n" for text in good[1:]]
                 rows_mal, side_mal = run(str(tmp_path / "nfs_malformed"), mal)
         finally:
-            _quit(procs)
+            H.quit(procs)
         want_side = [f"query.localhost{wid}{ext}" for wid in range(W)
                      for ext in ((".loads", ".res") if name == "loads" else (".res",))]
         assert side == want_side and side0 == want_side  # no .tmp left
