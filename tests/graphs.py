@@ -141,6 +141,89 @@ def comb(n, every, dmax, reach, seed):
     return graph_from_edges(n, edges)
 
 
+# dmax -> (lowest out-degree, first-move set bits, bits per move)
+BAND = {2: (2, 4, 1), 4: (3, 4, 2), 8: (5, 8, 4), 15: (9, 16, 4)}
+BAND_REACH = 40
+BAND_TAIL = 80
+
+
+def band(n, dmax, seed):
+    """A one-way ring a -> (a + 1) % n (strongly connected at any n >= 2) with
+    every node's out-degree in the band of one adjacency width: exactly 2 for
+    dmax = 2, 3..4, 5..8 and 9..15 for dmax = 4, 8 and 15.  The extra edges go
+    to distinct nodes within +-BAND_REACH positions; weights 1..29, so rows
+    hold many short runs (lattice_wide's reasoning).  A graph of any n at any
+    width: what the size-edge tests need (tests/test_gpu_size_edges.py).
+
+    The ring edge is every node's last edge, the one the DFS preorder follows
+    first: column == node id.  One node among the first 32 and one among the
+    last 32 get out-degree dmax itself.  From 2 * BAND_TAIL nodes on, the last
+    BAND_TAIL nodes all have out-degree dmax, a ring edge of weight 1 and
+    extra edges that go backwards only.  No edge from before the tail lands
+    in its last BAND_TAIL - BAND_REACH nodes, so towards a target just past
+    the wrap those take the ring edge, move dmax - 1 in every one of them: such
+    rows end in a single run over the whole last 32-column segment — while
+    towards the targets behind them the same nodes pick among their extra
+    edges, and rows end in a run that starts at column n - 1."""
+    lo = BAND[dmax][0]
+    assert n >= 2 and min(n - 1, BAND_REACH) >= dmax - 1
+    rng = np.random.default_rng(seed)
+    tail = n - BAND_TAIL if n >= 2 * BAND_TAIL else n
+    deg = rng.integers(lo, dmax + 1, n)
+    deg[int(rng.integers(0, min(32, n)))] = dmax
+    deg[n - 1 - int(rng.integers(0, min(32, n)))] = dmax
+    deg[tail:] = dmax
+    edges = []
+    for a in range(n):
+        near = sorted({(a + d) % n for d in range(-BAND_REACH, 0 if a >= tail else BAND_REACH + 1)}
+                      - {a})
+        for i in rng.choice(len(near), size=int(deg[a]) - 1, replace=False):
+            edges.append((a, near[i], int(rng.integers(1, 30))))
+        edges.append((a, (a + 1) % n, 1 if a >= tail else int(rng.integers(1, 30))))
+    return graph_from_edges(n, edges)
+
+
+# The size-edge cases of tests/test_gpu_size_edges.py: column counts on and
+# one off the 32-column segment and the 2048-column tile, at every adjacency
+# width.  test_oracle_cpu.py pins, from the oracle alone, what the GPU tests
+# rely on.  Not in GRAPHS, for the reason above.
+EDGE_N = (31, 32, 33, 2047, 2048, 2049, 4095, 4096, 4097)
+EDGE_DMAX = (2, 4, 8, 15)
+EDGE_TARGETS = 1100
+
+
+def edge_graph(n, dmax):
+    return band(n, dmax, seed=100 * n + dmax)
+
+
+def edge_targets(order, k=EDGE_TARGETS):
+    """min(n, k) shuffled nodes that always hold the nodes at columns 0, 1,
+    n - 2 and n - 1 (order[node] = column)."""
+    n = len(order)
+    col_node = np.argsort(order)
+    forced = np.unique(col_node[[0, 1, n - 2, n - 1]])
+    rng = np.random.default_rng(n)
+    rest = rng.permutation(n)
+    rest = rest[~np.isin(rest, forced)][:max(0, min(n, k) - len(forced))]
+    t = np.concatenate([forced, rest]).astype(np.uint32)
+    rng.shuffle(t)
+    return t
+
+
+def edge_queries(order, targets, nq):
+    """nq seeded (source, target) pairs over `targets`; the first six have the
+    nodes at columns 0 and n - 1 as source and as target, in every pairing."""
+    n = len(order)
+    col_node = np.argsort(order)
+    rng = np.random.default_rng(2)
+    s = rng.integers(0, n, nq).astype(np.uint32)
+    t = targets[rng.integers(0, len(targets), nq)].copy()
+    first, last = col_node[0], col_node[n - 1]
+    s[:6] = [first, last, first, last, first, last]
+    t[:4] = [last, first, first, last]
+    return s, t
+
+
 # name -> (graph, first-move set bits, 2048-column tiles, targets the GPU test builds)
 WIDE = {
     "lattice8": (lambda: lattice_wide(80, 80, 8, seed=8), 8, 4, 2500),

@@ -106,16 +106,22 @@ def test_switch_off_bit_exact(switch):
 #            budget, so the gated rle_scan<4> re-counts the batch
 #   hub8     the same path with a degree-8 node: rle_scan<8> + rle_moves<8>
 #            (what the switch must leave alone)
+#   band2048 graphs.band, 2048 nodes, 1029 targets: one tile with no padded
+#            column, a second batch of five rows
+#   band2049 2049 nodes: a second tile of one column and 2047 padded ones
+#            (both pinned by test_oracle_cpu.py with the other size-edge cases)
 CHILD_UNFUSED = r"""
 import json, sys
 import numpy as np
 sys.path[:0] = [%r, %r, %r]
 import cpd, oracle
-from graphs import chain_graph, chain_hub
+from graphs import chain_graph, chain_hub, edge_graph
 out = {}
 for name, make, k in (("synth70", lambda: cpd.synth_road_graph(70, 70, seed=70), 1500),
                       ("chain", lambda: chain_graph(34000, seed=34), 300),
-                      ("hub8", lambda: chain_hub(34000, 8, seed=8), 300)):
+                      ("hub8", lambda: chain_hub(34000, 8, seed=8), 300),
+                      ("band2048", lambda: edge_graph(2048, 4), 1029),
+                      ("band2049", lambda: edge_graph(2049, 4), 1029)):
     g = make()
     plan = cpd.Plan(g)
     dev = cpd.Graph(plan, batch=1024)
@@ -143,7 +149,8 @@ def test_unfused_rle_past_one_tile():
     assert p.returncode == 0, p.stderr[-2000:]
     res = json.loads(p.stdout.strip().splitlines()[-1])
     shape = {k: (v["tiles"], v["bits"]) for k, v in res.items()}
-    assert shape == {"synth70": (3, 2), "chain": (17, 1), "hub8": (17, 4)}, shape
+    assert shape == {"synth70": (3, 2), "chain": (17, 1), "hub8": (17, 4), "band2048": (1, 2),
+                     "band2049": (2, 2)}, shape
     assert res["chain"]["runs_per_row"] < 8 and res["hub8"]["runs_per_row"] < 16
     for name, v in res.items():
         assert v["offsets"] and v["runs"] and v["moves"], (name, v)

@@ -281,3 +281,93 @@ def test_wide_degree_generators_keep_their_shape(name):
         assert per_row.min() > 0.3 * g.n
     for t in targets[:3]:  # strongly connected
         assert oracle.reverse_dijkstra(g.row_ptr, g.dst, g.w, t).max() != oracle.INF
+
+
+def _last_run_starts(off, runs):
+    return (runs[off[1:].astype(np.int64) - 1] >> 4).astype(np.int64)
+
+
+@pytest.mark.parametrize("dmax", [2, 4, 8, 15])
+@pytest.mark.parametrize("n", [31, 32, 33, 2047, 2048, 2049, 4095, 4096, 4097])
+def test_size_edge_cases_hold_what_they_are_named_for(n, dmax):
+    """What tests/test_gpu_size_edges.py relies on, from the oracle alone:
+    (a) the out-degree band and the widths that follow from it, (b) the padded
+    columns, (c) rows whose last run starts at column n - 1 and rows whose
+    last run starts more than 32 columns before n, (d) a run start on a tile's
+    first column, (e) targets and query sources at columns 0 and n - 1.
+    At n <= 33 no last run can start more than 32 columns before n unless the
+    row is a single run, which these graphs' rows never are: there (c) asks
+    for a last run that starts before column n - 1."""
+    from graphs import BAND, EDGE_DMAX, EDGE_N, edge_graph, edge_queries, edge_targets
+    assert n in EDGE_N and dmax in EDGE_DMAX
+    g = edge_graph(n, dmax)
+    lo, set_bits, move_bits = BAND[dmax]
+    deg = np.diff(g.row_ptr.astype(np.int64))
+    # (a)
+    assert deg.min() >= lo and deg.max() == dmax
+    assert (lo, dmax) in ((2, 2), (3, 4), (5, 8), (9, 15))
+    shift = int(np.ceil(np.log2(deg.max())))          # log2 of the adjacency slots
+    assert (4 if shift <= 2 else 1 << shift) == set_bits
+    assert (1 if dmax <= 2 else 2 if dmax <= 4 else 4) == move_bits
+    order = oracle.dfs_preorder(g.row_ptr, g.dst)
+    np.testing.assert_array_equal(order, np.arange(n))  # column == node id
+    np.testing.assert_array_equal(cpd.Plan(g).order(), order)
+    assert (deg[order < 32] == dmax).any() and (deg[order >= n - 32] == dmax).any()
+    # (b)
+    npad = (n + 2047) // 2048 * 2048
+    assert npad - n == {31: 2017, 32: 2016, 33: 2015, 2047: 1, 2048: 0, 2049: 2047,
+                        4095: 1, 4096: 0, 4097: 2047}[n]
+    targets = edge_targets(order)
+    assert len(targets) == min(n, 1100) == len(np.unique(targets))
+    off, runs = oracle.build_rows(g.row_ptr, g.dst, g.w, order, targets)
+    # (c); the first kind also in a row that is not the last (the index test
+    # cuts its chunks behind such a row)
+    last = _last_run_starts(off, runs)
+    assert (last[:-1] == n - 1).any()
+    assert (last < n - 32).any() if n > 33 else (last < n - 1).any()
+    # (d)
+    starts = runs >> 4
+    if n > 2048:
+        assert ((starts > 0) & (starts % 2048 == 0)).any()
+        if n == 4097:
+            assert (starts == 2048).any() and (starts == 4096).any()
+    # (e)
+    tcol = order[targets]
+    assert {0, 1, n - 2, n - 1} <= set(tcol.tolist())
+    s, t = edge_queries(order, targets, 3000)
+    pairs = set(zip(order[s[:6]].tolist(), order[t[:6]].tolist()))
+    assert {(0, n - 1), (n - 1, 0), (0, 0), (n - 1, n - 1)} <= pairs
+    assert np.isin(t, targets).all()
+    for v in targets[:3]:  # strongly connected
+        assert oracle.reverse_dijkstra(g.row_ptr, g.dst, g.w, v).max() != oracle.INF
+
+
+@pytest.mark.parametrize("dmax", [2, 4, 8, 15])
+def test_size_edge_row_count_targets(dmax):
+    """The shuffled node order the row-count tests of test_gpu_size_edges.py
+    build from (at n = 2049): its short batches hold rows of both kinds of (c)
+    above and none of the full batch's targets."""
+    from graphs import edge_graph
+    n = 2049
+    g = edge_graph(n, dmax)
+    order = oracle.dfs_preorder(g.row_ptr, g.dst)
+    perm = np.random.default_rng(dmax).permutation(n).astype(np.uint32)
+    short = perm[1024:1024 + 31]      # the six short batches, back to back
+    off, runs = oracle.build_rows(g.row_ptr, g.dst, g.w, order, short)
+    last = _last_run_starts(off, runs)
+    assert (last == n - 1).any() and (last < n - 32).any()
+    assert not np.isin(short, perm[:1024]).any()
+
+
+@pytest.mark.parametrize("n,tiles", [(32768, 16), (32769, 17)])
+def test_move_chunk_cases_keep_their_shape(n, tiles):
+    """chain_hub at exactly 16 tiles and one column more: 8-bit sets, a
+    handful of runs per row."""
+    from graphs import chain_hub
+    g = chain_hub(n, 8, seed=8)
+    assert (g.n + 2047) // 2048 == tiles
+    assert 5 <= int(np.diff(g.row_ptr.astype(np.int64)).max()) <= 8
+    order = oracle.dfs_preorder(g.row_ptr, g.dst)
+    targets = np.random.default_rng(1).permutation(g.n).astype(np.uint32)[:100]
+    off, runs = oracle.build_rows(g.row_ptr, g.dst, g.w, order, targets)
+    assert np.diff(off.astype(np.int64)).max() < 16
