@@ -45,7 +45,8 @@ ALPHA_MAX = 64881
 EXPORTED = [
     "cpd_last_error", "cpd_version", "cpd_partition", "cpd_partition_nbuckets",
     "cpd_dfs_preorder", "cpd_synth_road_graph", "cpd_synth_congestion",
-    "cpd_plan_create", "cpd_plan_info_get", "cpd_plan_order", "cpd_plan_export_ch",
+    "cpd_plan_create", "cpd_hierarchy_create", "cpd_plan_info_get", "cpd_plan_order",
+    "cpd_plan_export_ch",
     "cpd_plan_save", "cpd_plan_load", "cpd_plan_free", "cpd_device_count",
     "cpd_graph_create", "cpd_graph_set_batch", "cpd_graph_get_batch", "cpd_graph_free",
     "cpd_build_rows", "cpd_rows_count", "cpd_rows_export", "cpd_rows_export_range",
@@ -388,17 +389,20 @@ def synth_congestion(w, frac=0.1, lo=1.0, hi=3.0, seed=3) -> np.ndarray:
 class Plan:
     def __init__(self, g: RoadGraph | None = None, threads: int = 0, settle: int = 0,
                  verbose: bool = False, hierarchy: bool = True, gpu: int | None = None,
-                 _handle=None):
-        """gpu: contract the hierarchy on this device (None: host threads)."""
+                 ch_only: bool = False, _handle=None):
+        """gpu: contract the hierarchy on this device (None: host threads).
+        ch_only: the contraction alone, at any out-degree (cpd_hierarchy_create):
+        only info() and export_ch() take such a plan."""
         self._h = C.c_void_p()
         if _handle is not None:
             self._h = _handle
         else:
             opts = PlanOpts(threads, settle, int(verbose), int(not hierarchy),
                             int(gpu is not None), int(gpu or 0))
-            _check(lib.cpd_plan_create(_ptr(g.row_ptr, u32p), _ptr(g.dst, u32p),
-                                       _ptr(g.w, u32p), C.c_uint32(g.n), C.c_uint32(g.m),
-                                       C.byref(opts), C.byref(self._h)))
+            create = lib.cpd_hierarchy_create if ch_only else lib.cpd_plan_create
+            _check(create(_ptr(g.row_ptr, u32p), _ptr(g.dst, u32p),
+                          _ptr(g.w, u32p), C.c_uint32(g.n), C.c_uint32(g.m),
+                          C.byref(opts), C.byref(self._h)))
 
     @classmethod
     def load(cls, path: str) -> "Plan":

@@ -161,6 +161,16 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
     CPD_REQUIRE(2ull * M < (1ull << 32), CPD_E_RANGE, "GPU contraction: graph has >= 2^31 arcs");
     size_t arena_cap = std::min<size_t>(std::max<size_t>(16ull * M, 1u << 22),
                                         (1ull << 32) - 1);  // arcs
+    size_t pool_cap = 2ull * std::max<size_t>(M, 1024);     // arcs, of each pool
+    // test knob: "arena,pool" capacities in arcs (the arena keeps room for the
+    // initial lists), so that small graphs compact the arena and grow the pools
+    if (const char* e = std::getenv("CPD_CH_ARENA")) {
+        unsigned long long a = 0, b = 0;
+        if (std::sscanf(e, "%llu,%llu", &a, &b) == 2 && a && b) {
+            arena_cap = std::min<size_t>(std::max<size_t>(a, 2ull * M), arena_cap);
+            pool_cap = std::min<size_t>(b, pool_cap);
+        }
+    }
     DBuf<uint32_t> arena, arena2;
     arena.ensure(2 * arena_cap);
     CH_HIP(hipMemcpyAsync(arena.p, arena0.data(), arena0.size() * 4, hipMemcpyHostToDevice, st));
@@ -198,8 +208,8 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
     rec_uo.ensure(n);
     rec_do.ensure(n);
     DBuf<uint32_t> upool, dpool, pairs, slots, sflag, spos, sclist, bk_o, bk_i, ovf, ovf2, ctr;
-    upool.ensure(2ull * std::max<size_t>(M, 1024) * 2);
-    dpool.ensure(2ull * std::max<size_t>(M, 1024) * 2);
+    upool.ensure(2 * pool_cap);
+    dpool.ensure(2 * pool_cap);
     ctr.ensure(8);
     CH_HIP(hipMemsetAsync(ctr.p, 0, 32, st));
     CH_HIP(hipMemcpyAsync(ctr.p + 2, &maxdeg0, 4, hipMemcpyHostToDevice, st));
@@ -245,6 +255,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
     ws1.ensure(lb1 * lanes1);
     CH_HIP(hipMemsetAsync(ws1.p, 0, ws1.n, st));
     uint32_t tag1 = 0, tag2 = 0;
+    chk::WitnessCaps caps2_last{0, 0, 0};  // the caps ws2 was last cleared for
     uint64_t searches = 0, big_searches = 0;
 
     auto overlay = [&]() {
@@ -265,7 +276,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
     // pops + relaxations a lane search may take before a wave takes it over
     // (A/B at 1M nodes: 512 -> 2.6 s, 2048 -> 2.4 s, none -> 2.1 s: none kept)
     constexpr uint32_t lane_cap = 0xFFFFFFFFu;
-    uint64_t wave_searches = 0;
+    uint64_t wave_searches = 0, wave_size_searches[3] = {0, 0, 0};
     double t_lane = 0, t_wave = 0, t_big = 0;  // witness kernel wall times (verbose)
     DBuf<uint32_t> ovf3;
     auto witness = [&](uint32_t np, bool contract, uint32_t settle) {
@@ -303,6 +314,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
                                      wave_blocks, size, slots.p, sflag.p, sc.p, out.p, ctr.p + 4,
                                      st);
             wave_searches += cnt;
+            wave_size_searches[size] += cnt;
             read({ctr.p + 4});
             cnt = hv.p[0];
             list = out.p;
@@ -328,10 +340,16 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
         const uint32_t lanes2 =
             (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>((novf + 63) / 64 * 64,
                                                                 budget / lb2 / 64 * 64));
-        if (ws2.n < lb2 * lanes2 || (uint64_t)tag2 + novf + 1 >= (1ull << 32)) {
+        // a lane's tables lie where the caps put them: under other caps (the
+        // two settle limits alternate, the largest degree grows) a hash slot
+        // falls on what was heap or target words, which tags do not rule out
+        const bool moved = caps2.hash != caps2_last.hash || caps2.heap != caps2_last.heap ||
+                           caps2.tgt != caps2_last.tgt;
+        if (ws2.n < lb2 * lanes2 || moved || (uint64_t)tag2 + novf + 1 >= (1ull << 32)) {
             ws2.ensure(lb2 * lanes2);
             CH_HIP(hipMemsetAsync(ws2.p, 0, ws2.n, st));
             tag2 = 0;
+            caps2_last = caps2;
         }
         DBuf<uint32_t>& lost = list == ovf.p ? ovf2 : ovf;  // not the list being read
         lost.ensure(novf);
@@ -367,6 +385,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
 
     uint32_t R = n, rank0 = 0, round = 0;
     uint64_t utop = 0, dtop = 0;
+    uint32_t compactions = 0, ugrowths = 0, dgrowths = 0;
     double tph[5] = {0, 0, 0, 0, 0};  // pick, contract, record, lists, priorities (verbose)
     double ta = now_seconds();
     auto phase = [&](int k) {
@@ -400,6 +419,8 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
         witness(np, true, settle_c);
         phase(1);
         // 3. record ranks and hierarchy arcs; 4. neighbours' counters
+        ugrowths += 2 * (utop + nout) > upool.n;
+        dgrowths += 2 * (dtop + nin) > dpool.n;
         upool.grow(2 * (utop + nout), st);
         dpool.grow(2 * (dtop + nin), st);
         chk::launch_record(Sl.p, nS, rank0, overlay(), s[2].p, s[3].p, utop, dtop, rank.p, rec_v.p,
@@ -447,6 +468,7 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
             arena2.release();
             arena_cap = cap2;
             top = used;
+            ++compactions;
         }
         chk::launch_bucket_starts(Al.p, nA, s[2].p, s[3].p, bo_o.p, bo_i.p, st);
         bk_o.ensure(2ull * std::max(K, 1u));
@@ -541,12 +563,17 @@ Hierarchy build_hierarchy_gpu(uint32_t n, const uint32_t* row_ptr, const uint32_
         std::fprintf(stderr,
                      "[ch-gpu] %u rounds, %llu witness searches (%llu by waves, %llu in the large "
                      "workspace), "
+                     "wave sizes %llu / %llu / %llu, %u arena compactions, pool growths %u up "
+                     "%u down, "
                      "up arcs %llu, down arcs %llu, levels up %u down %u; setup %.2fs, initial "
                      "priorities %.2fs, rounds %.2fs (pick %.2f contract %.2f record %.2f lists "
                      "%.2f priorities %.2f; witness kernels: lane %.2f wave %.2f large %.2f), "
                      "assembly %.2fs\n",
                      round, (unsigned long long)searches, (unsigned long long)wave_searches,
                      (unsigned long long)big_searches,
+                     (unsigned long long)wave_size_searches[0],
+                     (unsigned long long)wave_size_searches[1],
+                     (unsigned long long)wave_size_searches[2], compactions, ugrowths, dgrowths,
                      (unsigned long long)H.up_off[n], (unsigned long long)H.dn_off[n], H.nlev_up,
                      H.nlev_dn, t_init - t0, t_prio0 - t_init, t_dev - t_prio0, tph[0], tph[1],
                      tph[2], tph[3], tph[4], t_lane, t_wave, t_big, now_seconds() - t_dev);

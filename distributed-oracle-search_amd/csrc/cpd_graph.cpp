@@ -616,6 +616,7 @@ int cpd_graph_create(const cpd_plan* p, int device, cpd_graph** out) {
     return guarded([&] {
         CPD_REQUIRE(p && out, CPD_E_ARG, "graph: null argument");
         *out = nullptr;
+        CPD_REQUIRE(p->order.size() == p->n, CPD_E_ARG, "plan holds a hierarchy only");
         require_device();
         const double tg0 = now_seconds();
         auto g = std::make_unique<cpd_graph>();

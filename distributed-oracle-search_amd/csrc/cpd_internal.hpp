@@ -39,9 +39,10 @@ int guarded(F&& body) {
     }
 }
 
-// Validate a CSR graph as the .xy loader would produce it.
+// Validate a CSR graph as the .xy loader would produce it.  any_degree: no
+// limit on the out-degree (cpd_hierarchy_create: no rows, so no move field).
 void check_csr(uint32_t n, uint32_t m, const uint32_t* row_ptr,
-               const uint32_t* dst, const uint32_t* w);
+               const uint32_t* dst, const uint32_t* w, bool any_degree = false);
 
 void dfs_preorder(uint32_t n, const uint32_t* row_ptr, const uint32_t* dst,
                   uint32_t* order);

@@ -30,7 +30,7 @@ double now_seconds() {
 }
 
 void check_csr(uint32_t n, uint32_t m, const uint32_t* row_ptr,
-               const uint32_t* dst, const uint32_t* w) {
+               const uint32_t* dst, const uint32_t* w, bool any_degree) {
     CPD_REQUIRE(row_ptr && (m == 0 || (dst && w)), CPD_E_ARG, "null graph array");
     CPD_REQUIRE(n > 0, CPD_E_ARG, "graph has no nodes");
     CPD_REQUIRE(n < (1u << 28), CPD_E_RANGE,
@@ -41,7 +41,7 @@ void check_csr(uint32_t n, uint32_t m, const uint32_t* row_ptr,
         CPD_REQUIRE(row_ptr[v] <= row_ptr[v + 1], CPD_E_ARG,
                     "row_ptr not monotone");
         uint32_t deg = row_ptr[v + 1] - row_ptr[v];
-        if (deg > CPD_MAX_DEGREE)
+        if (deg > CPD_MAX_DEGREE && !any_degree)
             throw Error(CPD_E_RANGE, "node " + std::to_string(v) + " has out-degree " +
                                          std::to_string(deg) +
                                          " > 15 (4-bit move field)");

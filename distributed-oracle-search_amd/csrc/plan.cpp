@@ -149,6 +149,28 @@ int cpd_plan_create(const uint32_t* row_ptr, const uint32_t* dst, const uint32_t
     });
 }
 
+int cpd_hierarchy_create(const uint32_t* row_ptr, const uint32_t* dst, const uint32_t* w,
+                         uint32_t n, uint32_t m, const cpd_plan_opts* opts, cpd_plan** out) {
+    return guarded([&] {
+        CPD_REQUIRE(out, CPD_E_ARG, "hierarchy: null output");
+        *out = nullptr;
+        CPD_REQUIRE(!(opts && opts->no_hierarchy), CPD_E_ARG, "hierarchy: no_hierarchy is set");
+        check_csr(n, m, row_ptr, dst, w, true);
+        auto p = std::make_unique<cpd_plan>();
+        p->n = n;
+        p->m = m;
+        const uint32_t settle = opts ? opts->witness_settle : 0;
+        const int verbose = opts ? opts->verbose : 0;
+        const double t0 = now_seconds();
+        if (opts && opts->ch_gpu)
+            p->ch = build_hierarchy_gpu(n, row_ptr, dst, w, opts->ch_device, settle, verbose);
+        else
+            p->ch = build_hierarchy(n, row_ptr, dst, w, opts ? opts->threads : 0, settle, verbose);
+        p->ch_seconds = now_seconds() - t0;
+        *out = p.release();
+    });
+}
+
 int cpd_plan_info_get(const cpd_plan* p, cpd_plan_info* info) {
     return guarded([&] {
         CPD_REQUIRE(p && info, CPD_E_ARG, "plan info: null argument");
@@ -168,6 +190,7 @@ int cpd_plan_info_get(const cpd_plan* p, cpd_plan_info* info) {
 int cpd_plan_order(const cpd_plan* p, uint32_t* order) {
     return guarded([&] {
         CPD_REQUIRE(p && order, CPD_E_ARG, "plan order: null argument");
+        CPD_REQUIRE(p->order.size() == p->n, CPD_E_ARG, "plan holds a hierarchy only");
         std::memcpy(order, p->order.data(), p->n * sizeof(uint32_t));
     });
 }
@@ -198,6 +221,7 @@ int cpd_plan_export_ch(const cpd_plan* p, uint32_t* rank, uint64_t* up_off,
 int cpd_plan_save(const cpd_plan* p, const char* path) {
     return guarded([&] {
         CPD_REQUIRE(p && path, CPD_E_ARG, "plan save: null argument");
+        CPD_REQUIRE(p->order.size() == p->n, CPD_E_ARG, "plan holds a hierarchy only");
         // a name of this process and call alone: concurrent savers (workers
         // started together, make_cpds.py:58-60) never truncate each other
         static std::atomic<unsigned> seq{0};

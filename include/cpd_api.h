@@ -158,6 +158,17 @@ typedef struct cpd_plan_info {
 int  cpd_plan_create(const uint32_t* row_ptr, const uint32_t* dst,
                      const uint32_t* w, uint32_t n, uint32_t m,
                      const cpd_plan_opts* opts, cpd_plan** out);
+/* The contraction alone, on a graph of any out-degree: a plan's limit of
+ * CPD_MAX_DEGREE comes from the move field of its rows, and the contraction
+ * meets far larger degrees in the overlay of any road graph.  The same two
+ * builders under the same options (no_hierarchy is refused), but a GPU
+ * contraction that fails is an error here, with no host build in its place.
+ * The plan returned holds the hierarchy and nothing else: cpd_plan_info_get
+ * (dist_bound 0), cpd_plan_export_ch and cpd_plan_free take it, every other
+ * call refuses it with CPD_E_ARG.  For checks of the contraction.           */
+int  cpd_hierarchy_create(const uint32_t* row_ptr, const uint32_t* dst,
+                          const uint32_t* w, uint32_t n, uint32_t m,
+                          const cpd_plan_opts* opts, cpd_plan** out);
 int  cpd_plan_info_get(const cpd_plan* p, cpd_plan_info* info);
 int  cpd_plan_order(const cpd_plan* p, uint32_t* order /* n */);
 /* Export the hierarchy in NODE space (for CPU-side checks):

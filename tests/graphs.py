@@ -316,6 +316,72 @@ def wide_level1(ch):
     return v, cnt[v]
 
 
+# Contraction gadgets: witness searches with many targets on graphs that
+# contract in a fraction of a second (tests/test_gpu_ch_edges.py;
+# test_ch_edges_cpu.py pins, from the host plan alone, what the GPU tests rely
+# on).  Not in GRAPHS, for the reason above.
+
+def ch_hub(n0, D, Din, seed, wmax=3):
+    """chain_graph's path (weights 1..wmax) whose middle node, the hub, has
+    out-degree exactly D (D - 2 extra arcs to distinct chain nodes) and Din
+    extra in-arcs from chain nodes outside its out-list.  The hub is contracted
+    last, so its searches are simulations: one per in-neighbour, with D targets
+    from an extra in-neighbour (D - 1 from a path neighbour).  wmax = 2: most
+    targets tie on their via weight.  Returns (graph, hub)."""
+    rng = np.random.default_rng(seed)
+    edges = _path_edges(n0, rng, wmax)
+    hub = n0 // 2
+    far = np.array([x for x in range(n0) if abs(x - hub) > 1])
+    pick = rng.choice(far, size=D - 2 + Din, replace=False)
+    for b in pick[:D - 2]:
+        edges.append((hub, int(b), int(rng.integers(1, wmax + 1))))
+    for a in pick[D - 2:]:
+        edges.append((int(a), hub, int(rng.integers(1, wmax + 1))))
+    return graph_from_edges(n0, edges), hub
+
+
+def ch_fan(n0, D, F, seed, wmax=3):
+    """chain_graph's path (weights 1..wmax) and F fan nodes n0 .. n0 + F - 1.
+    Fan f has one in-arc, from chain node u_f with weight 1, and D out-arcs of
+    weight 10 to distinct chain nodes x more than one position from u_f; a
+    direct arc u_f -> x of weight 1..wmax witnesses every one of them.  A fan
+    needs no shortcut (edge difference -(D + 1)): it is contracted early, all
+    D out-neighbours still there — one contraction search of exactly D
+    targets, all tied on via = 11 — and u_f keeps out-degree D + 3.  Returns
+    (graph, fan node ids)."""
+    rng = np.random.default_rng(seed)
+    edges = _path_edges(n0, rng, wmax)
+    fans = np.arange(n0, n0 + F)
+    for f in range(F):
+        u = (f + 1) * n0 // (F + 1)
+        far = np.array([x for x in range(n0) if abs(x - u) > 1])
+        edges.append((u, n0 + f, 1))
+        for x in rng.choice(far, size=D, replace=False):
+            edges.append((n0 + f, int(x), 10))
+            edges.append((u, int(x), int(rng.integers(1, wmax + 1))))
+    return graph_from_edges(n0 + F, edges), fans
+
+
+# the degrees test_gpu_ch_edges.py runs: one below, on and one past the lane
+# workspace's 32 targets and the wave kernel's 64 and 128, and far past them
+CH_FAN_D = (31, 32, 33, 64, 65, 128, 129, 300)
+CH_HUB_D = (33, 65, 129, 300)
+CH_TIE_D = (65, 300)
+CH_LANE_EDGE_D = (32, 33)   # hubs, with every search started in the lane kernel
+
+
+def ch_fan_case(D, wmax=3):
+    return ch_fan(1000, D, 3, seed=D, wmax=wmax)
+
+
+def ch_hub_case(D, wmax=3):
+    return ch_hub(1000, D, 1, seed=D, wmax=wmax)
+
+
+def ch_hub_two_way():
+    return ch_hub(2000, 300, 300, seed=7)
+
+
 GRAPHS = {
     "synth": lambda: cpd.synth_road_graph(40, 30, seed=7),
     "ties": tie_graph,

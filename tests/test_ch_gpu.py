@@ -3,8 +3,12 @@ host build's (ch.cpp), rank for rank and arc for arc: same priorities, same
 independent sets, same witness-search cut-offs (the GPU heap replays
 libstdc++'s push_heap / pop_heap), same shortcut merges.  Every array the
 plan exports is compared; rows built from either plan are then the same by
-construction (they are a function of exact distances in any case)."""
+construction (they are a function of exact distances in any case).  The
+graphs here are road-like (out-degree <= 15, a few dozen targets per search
+at the most); test_gpu_ch_edges.py takes the contraction past its workspace
+caps, through arena compaction and pool growth."""
 import os
+import re
 import subprocess
 import sys
 import time
@@ -55,26 +59,59 @@ def test_ch_gpu_identical_spec_graph():
     same_hierarchy(cpd.Plan(g).export_ch(), cpd.Plan(g, gpu=0).export_ch())
 
 
+# the verbose contraction's last line: where the searches ran, what was resized
+SUMMARY = re.compile(
+    r"\[ch-gpu\] (?P<rounds>\d+) rounds, (?P<searches>\d+) witness searches "
+    r"\((?P<waves>\d+) by waves, (?P<large>\d+) in the large workspace\), "
+    r"wave sizes (?P<w0>\d+) / (?P<w1>\d+) / (?P<w2>\d+), (?P<compactions>\d+) arena "
+    r"compactions, pool growths (?P<up>\d+) up (?P<down>\d+) down,")
+
+
+def summary(stderr):
+    """The one summary line of a verbose GPU contraction, as a dict of ints (a
+    contraction that failed and was redone on the host prints none)."""
+    found = list(SUMMARY.finditer(stderr))
+    assert len(found) == 1, stderr[-2000:]
+    s = {k: int(v) for k, v in found[0].groupdict().items()}
+    assert s["w0"] + s["w1"] + s["w2"] == s["waves"]
+    return s
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("env", [{"CPD_CH_WS": "16,8,2"},
                                  {"CPD_CH_WS": "16,8,2", "CPD_CH_NOWAVE": "1"},
                                  {"CPD_CH_WAVE": "0"}, {"CPD_CH_WAVE": "1000000000"},
-                                 {"CPD_CH_WAVE": "1000000000", "CPD_CH_TINY": "0"}])
+                                 {"CPD_CH_WAVE": "1000000000", "CPD_CH_TINY": "0"},
+                                 {"CPD_CH_WS": "16,8,2", "CPD_CH_WAVE": "0"}])
 def test_ch_gpu_search_routes(env):
     """Every route a witness search can take — the lane workspace (here tiny,
     so most searches overflow it), the wave kernel's LDS, the large HBM
-    workspace sized from the largest degree — gives the same hierarchy."""
+    workspace sized from the largest degree — gives the same hierarchy, and
+    the summary line shows that the route carried searches.  (A round of up to
+    65536 searches skips the lane kernel, so on this graph CPD_CH_WS acts only
+    beside CPD_CH_WAVE=0 or CPD_CH_NOWAVE.)"""
     code = (
         "import sys; sys.path[:0] = %r\n"
         "import numpy as np, cpd\n"
         "g = cpd.synth_road_graph(80, 60, seed=9)\n"
-        "a = cpd.Plan(g).export_ch(); b = cpd.Plan(g, gpu=0).export_ch()\n"
+        "a = cpd.Plan(g).export_ch(); b = cpd.Plan(g, gpu=0, verbose=True).export_ch()\n"
         "assert all(np.array_equal(a[k], b[k]) for k in a), 'differs'\n"
         "print('ok')\n" % (sys.path[:3],))
-    env = dict(os.environ, **env)
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True,
-                       timeout=300)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env),
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
+    s = summary(r.stderr)
+    print(env, s)
+    if "CPD_CH_NOWAVE" in env:
+        assert s["waves"] == 0 and s["large"] >= 1
+    elif env.get("CPD_CH_WAVE") == "0":
+        assert s["searches"] > 0 and s["waves"] >= ("CPD_CH_WS" in env)
+    else:
+        assert s["waves"] >= 1
+    if env.get("CPD_CH_TINY") == "0":
+        assert s["w0"] == 0
+    elif env.get("CPD_CH_WAVE") == "1000000000":
+        assert s["w0"] >= 1
 
 
 @pytest.mark.gpu
