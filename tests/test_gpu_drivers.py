@@ -3,6 +3,7 @@ the reference drivers drive warthog's (make_cpds.py:20, make_fifos.py:21,
 process_query.py:35-111), with `ssh host 'bash -s'` replaced by local bash
 (tests/driver_harness.py; bytes pinned by tests/golden/driver_fixtures.json).
 The answers and per-query side files are checked against the CPU oracle."""
+import json
 import os
 import subprocess
 import time
@@ -219,3 +220,47 @@ def test_make_cpd_auto_pipeline_matches_sequential(tmp_path, method, key, fmt):
         o_off, o_runs = oracle.build_rows(g.row_ptr, g.dst, g.w, order, np.array(targets))
         np.testing.assert_array_equal(counts, np.diff(o_off))
         np.testing.assert_array_equal(moves, oracle.moves_from_runs(o_off, o_runs, g.n, bits))
+
+
+JSON_KEYS = ["worker", "maxworker", "rows", "runs", "batch", "discard", "read_s", "plan_s",
+             "plan_cached", "graph_s", "batch_alloc_s", "setup_s", "rows_s", "build_calls_s",
+             "wait_s", "free_s", "export_bytes", "export_thread_s", "export_span_s",
+             "write_thread_s", "format", "arena_GB", "arena_s", "arena_wait_s", "total_s"]
+
+
+def test_make_cpd_auto_arena_plan_and_discard_variants(tmp_path):
+    """The ways of committing HBM (--no-arena, --arena-touch) and of getting the
+    plan (--no-plan-cache) change no byte of any file the default run writes;
+    --discard builds and exports the same rows and writes no bucket.  Every
+    run's machine-readable line parses and has its keys in their order."""
+    prefix = str(tmp_path / "g")
+    subprocess.run([os.path.join(BIN, "gen_synth"), "--width", "64", "--height", "48", "--seed",
+                    "5", "--out", prefix, "--queries", "10"], check=True, capture_output=True)
+
+    def run(mode, extra):
+        out = str(tmp_path / mode)
+        p = subprocess.run([os.path.join(BIN, "make_cpd_auto"), "--input", prefix + ".xy",
+                            "--partmethod", "mod", "--partkey", "5", "--workerid", "1",
+                            "--maxworker", "2", "--outdir", out, "--device", "0", "--batch",
+                            "1024", "--plan", str(tmp_path / "g.plan")] + extra,
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr
+        line, = [ln for ln in p.stdout.splitlines() if ln.startswith("make_cpd_auto-json: ")]
+        rec = json.loads(line[len("make_cpd_auto-json: "):])
+        assert list(rec) == JSON_KEYS
+        files = {f: open(os.path.join(out, f), "rb").read() for f in sorted(os.listdir(out))}
+        return rec, files
+
+    base, files = run("base", [])
+    assert base["discard"] is False
+    assert base["rows"] == len([x for x in range(64 * 48) if x % 5 in (1, 3)])
+    assert sum(f.endswith(".cpd") for f in files) == 2 and any(f.endswith(".order") for f in files)
+    for mode in ["--no-arena", "--arena-touch", "--no-plan-cache"]:
+        rec, got = run(mode, [mode])  # the first two load the plan the base run cached
+        assert got == files, mode
+        assert rec["rows"] == base["rows"] and rec["runs"] == base["runs"]
+        assert rec["plan_cached"] is (mode != "--no-plan-cache")
+    rec, got = run("--discard", ["--discard"])
+    assert not [f for f in got if ".cpd" in f]
+    assert rec["discard"] is True and rec["rows"] == base["rows"] and rec["runs"] == base["runs"]
+    assert rec["export_bytes"] == rec["rows"] * 192 * 4  # 3072 columns at 2 bits: 192 words
