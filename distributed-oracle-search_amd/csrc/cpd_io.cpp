@@ -47,8 +47,14 @@ struct Line {
         bool neg = false;
         if (*p == '-' || *p == '+') neg = *p++ == '-';
         if (p >= e || *p < '0' || *p > '9') return false;
+        // a magnitude past int64 saturates (no wrap): every caller's range
+        // check then refuses it
+        const int64_t top = INT64_MAX;
         int64_t r = 0;
-        while (p < e && *p >= '0' && *p <= '9') r = r * 10 + (*p++ - '0');
+        while (p < e && *p >= '0' && *p <= '9') {
+            const int d = *p++ - '0';
+            r = r > (top - d) / 10 ? top : r * 10 + d;
+        }
         v = neg ? -r : r;
         return true;
     }
@@ -65,10 +71,32 @@ void for_lines(const std::string& s, F&& f) {
     }
 }
 
-uint32_t to_u32(int64_t v, const std::string& what) {
-    if (v < 0 || v > 0xFFFFFFFFll) throw Error(CPD_E_IO, what + " out of range");
+// `where`: the file and line, "path: line 12"
+uint32_t to_u32(int64_t v, const std::string& where, const char* what) {
+    if (v < 0 || v > 0xFFFFFFFFll) throw Error(CPD_E_IO, where + ": " + what + " out of range");
     return (uint32_t)v;
 }
+
+int32_t to_i32(int64_t v, const std::string& where, const char* what) {
+    if (v < INT32_MIN || v > INT32_MAX) throw Error(CPD_E_IO, where + ": " + what + " out of range");
+    return (int32_t)v;
+}
+
+std::string at_line(const std::string& path, size_t lineno) {
+    return path + ": line " + std::to_string(lineno + 1);
+}
+
+// The size of an open file; the stream is left at its start.
+uint64_t stream_size(std::ifstream& f) {
+    f.seekg(0, std::ios::end);
+    const std::streamoff size = f.tellg();
+    f.seekg(0);
+    return size < 0 ? 0 : (uint64_t)size;
+}
+
+// More nodes than check_csr admits (the 28-bit run start column) are refused
+// at the header, before the per-node arrays are sized by it.
+constexpr int64_t kMaxNodes = (int64_t(1) << 28) - 1;
 
 const char kBucketMagic[8] = {'D', 'O', 'S', 'C', 'P', 'D', '0', '1'};
 const char kOrderMagic[8] = {'D', 'O', 'S', 'O', 'R', 'D', '0', '1'};
@@ -93,19 +121,29 @@ XYGraph read_xy(const std::string& path) {
             std::string et;
             if (!probe.i64(n) || !probe.word(et) || et != "edges" || !probe.i64(m))
                 throw Error(CPD_E_IO, path + ": bad header line " + std::to_string(lineno + 1));
+            if (n < 0 || n > kMaxNodes)
+                throw Error(CPD_E_IO, at_line(path, lineno) + ": node count out of range (at most " +
+                                          std::to_string(kMaxNodes) + ")");
+            if (m < 0 || m > 0xFFFFFFFFll)
+                throw Error(CPD_E_IO, at_line(path, lineno) + ": edge count out of range");
             hn = n;
             hm = m;
-            edges.reserve((size_t)m);
+            // no more than the file can hold ("e 0 0 0\n" is 8 bytes)
+            edges.reserve((size_t)std::min<uint64_t>((uint64_t)m, s.size() / 8 + 1));
         } else if (tag == "v") {
             int64_t id, x, y;
             if (!probe.i64(id) || !probe.i64(x) || !probe.i64(y))
                 throw Error(CPD_E_IO, path + ": bad v line " + std::to_string(lineno + 1));
-            verts.push_back({to_u32(id, "node id"), {(int32_t)x, (int32_t)y}});
+            const std::string at = at_line(path, lineno);
+            verts.push_back({to_u32(id, at, "node id"),
+                             {to_i32(x, at, "x coordinate"), to_i32(y, at, "y coordinate")}});
         } else if (tag == "e") {
             int64_t a, b, w;
             if (!probe.i64(a) || !probe.i64(b) || !probe.i64(w))
                 throw Error(CPD_E_IO, path + ": bad e line " + std::to_string(lineno + 1));
-            edges.push_back({to_u32(a, "edge tail"), to_u32(b, "edge head"), to_u32(w, "edge cost")});
+            const std::string at = at_line(path, lineno);
+            if (edges.size() == 0xFFFFFFFFull) throw Error(CPD_E_IO, at + ": more than 2^32 - 1 edges");
+            edges.push_back({to_u32(a, at, "edge tail"), to_u32(b, at, "edge head"), to_u32(w, at, "edge cost")});
         }
         // anything else (comments) is ignored
     });
@@ -122,7 +160,7 @@ XYGraph read_xy(const std::string& path) {
         g.x[v.first] = v.second.first;
         g.y[v.first] = v.second.second;
     }
-    g.row_ptr.assign(g.n + 1, 0);
+    g.row_ptr.assign((size_t)g.n + 1, 0);
     for (auto& e : edges) {
         if (e.a >= g.n || e.b >= g.n) throw Error(CPD_E_IO, path + ": edge endpoint out of range");
         g.row_ptr[e.a + 1]++;
@@ -166,16 +204,21 @@ std::vector<uint32_t> read_diff(const std::string& path, const XYGraph& g) {
         Line save = probe;
         if (!probe.word(tag)) return;
         Line nums = (tag == "e") ? probe : save;
-        if (tag != "e" && !(tag[0] >= '0' && tag[0] <= '9')) return;  // comment / header
+        // comment / header: anything but "e" or a number (a sign counts)
+        const bool sign = tag.size() > 1 && (tag[0] == '-' || tag[0] == '+');
+        const char d = tag[sign ? 1 : 0];
+        if (tag != "e" && !(d >= '0' && d <= '9')) return;
         int64_t a, b, c;
         if (!nums.i64(a) || !nums.i64(b) || !nums.i64(c))
             throw Error(CPD_E_IO, path + ": bad diff line " + std::to_string(lineno + 1));
-        uint32_t ua = to_u32(a, "diff tail"), ub = to_u32(b, "diff head");
+        const std::string at = at_line(path, lineno);
+        const uint32_t ua = to_u32(a, at, "diff tail"), ub = to_u32(b, at, "diff head");
+        const uint32_t uc = to_u32(c, at, "diff cost");
         if (ua >= g.n || ub >= g.n) throw Error(CPD_E_IO, path + ": diff node out of range");
         bool found = false;
         for (uint32_t e = g.row_ptr[ua]; e < g.row_ptr[ua + 1]; ++e)
             if (g.dst[e] == ub) {
-                w[e] = to_u32(c, "diff cost");
+                w[e] = uc;
                 found = true;
                 break;
             }
@@ -205,7 +248,8 @@ Pairs read_scen(const std::string& path) {
         int64_t a, b;
         if (!ln.i64(a) || !ln.i64(b))
             throw Error(CPD_E_IO, path + ": bad q line " + std::to_string(lineno + 1));
-        q.push_back({to_u32(a, "query source"), to_u32(b, "query target")});
+        const std::string at = at_line(path, lineno);
+        q.push_back({to_u32(a, at, "query source"), to_u32(b, at, "query target")});
     });
     return q;
 }
@@ -281,7 +325,7 @@ void read_query_file(const std::string& path, int threads, std::vector<uint32_t>
     const char* const b = text.data();
     const char* const e = b + text.size();
     // header: the query count (process_query.py:95); a file without one is empty
-    const char* body = static_cast<const char*>(std::memchr(b, '\n', text.size()));
+    const char* body = text.empty() ? nullptr : static_cast<const char*>(std::memchr(b, '\n', text.size()));
     body = body ? body + 1 : e;
     int64_t expect = 0;
     {
@@ -497,17 +541,16 @@ void BucketFile::close(uint64_t total) {
     if (std::rename(tmp_.c_str(), path_.c_str()) != 0) throw Error(CPD_E_IO, "rename failed: " + path_);
 }
 
-CpdBucket read_bucket_head(const std::string& path) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw Error(CPD_E_IO, "cannot open " + path);
-    const uint64_t size = (uint64_t)f.tellg();
-    f.seekg(0);
+// Header, targets and offsets of an open bucket file; `total` = its run count.
+// The file's size is checked against the header before anything is sized by it.
+static CpdBucket bucket_head(std::ifstream& f, const std::string& path, uint64_t& total) {
+    const uint64_t size = stream_size(f);
     char magic[8];
     f.read(magic, 8);
     if (!f || std::memcmp(magic, kBucketMagic, 8) != 0) throw Error(CPD_E_IO, path + ": not a CPD bucket file");
     CpdBucket b;
     uint32_t h32[6];
-    uint64_t total = 0;
+    total = 0;
     f.read(reinterpret_cast<char*>(h32), sizeof h32);
     f.read(reinterpret_cast<char*>(&total), 8);
     f.read(reinterpret_cast<char*>(&b.fingerprint), 8);
@@ -518,7 +561,8 @@ CpdBucket read_bucket_head(const std::string& path) {
     b.method = h32[3];
     b.key = h32[4];
     b.maxworker = h32[5];
-    if (size != kBucketHeader + 4ull * nrows + 8ull * (nrows + 1ull) + 4ull * total)
+    // (total <= size / 4 first: 4 * total must not wrap)
+    if (total > size / 4 || size != kBucketHeader + 4ull * nrows + 8ull * (nrows + 1ull) + 4ull * total)
         throw Error(CPD_E_IO, path + ": size does not match its header");
     b.targets.resize(nrows);
     b.offsets.resize((size_t)nrows + 1);
@@ -527,6 +571,13 @@ CpdBucket read_bucket_head(const std::string& path) {
     if (!f) throw Error(CPD_E_IO, path + ": truncated body");
     if (b.offsets[0] != 0 || b.offsets[nrows] != total) throw Error(CPD_E_IO, path + ": bad offsets");
     return b;
+}
+
+CpdBucket read_bucket_head(const std::string& path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw Error(CPD_E_IO, "cannot open " + path);
+    uint64_t total = 0;
+    return bucket_head(f, path, total);
 }
 
 void read_bucket_runs(const std::string& path, const CpdBucket& head, uint64_t first,
@@ -554,30 +605,11 @@ void read_bucket_runs(const std::string& path, const CpdBucket& head, uint64_t f
 CpdBucket read_bucket(const std::string& path) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw Error(CPD_E_IO, "cannot open " + path);
-    char magic[8];
-    f.read(magic, 8);
-    if (!f || std::memcmp(magic, kBucketMagic, 8) != 0) throw Error(CPD_E_IO, path + ": not a CPD bucket file");
-    CpdBucket b;
-    uint32_t h32[6];
     uint64_t total = 0;
-    f.read(reinterpret_cast<char*>(h32), sizeof h32);
-    f.read(reinterpret_cast<char*>(&total), 8);
-    f.read(reinterpret_cast<char*>(&b.fingerprint), 8);
-    if (!f) throw Error(CPD_E_IO, path + ": truncated header");
-    b.n = h32[0];
-    uint32_t nrows = h32[1];
-    b.bid = h32[2];
-    b.method = h32[3];
-    b.key = h32[4];
-    b.maxworker = h32[5];
-    b.targets.resize(nrows);
-    b.offsets.resize((size_t)nrows + 1);
+    CpdBucket b = bucket_head(f, path, total);
     b.runs.resize(total);
-    f.read(reinterpret_cast<char*>(b.targets.data()), nrows * 4ull);
-    f.read(reinterpret_cast<char*>(b.offsets.data()), (nrows + 1) * 8ull);
     f.read(reinterpret_cast<char*>(b.runs.data()), total * 4ull);
     if (!f) throw Error(CPD_E_IO, path + ": truncated body");
-    if (b.offsets[0] != 0 || b.offsets[nrows] != total) throw Error(CPD_E_IO, path + ": bad offsets");
     return b;
 }
 
@@ -659,7 +691,7 @@ MoveBucketFile::MoveBucketFile(const std::string& path, const MoveBucket& b, uin
         const uint32_t st[2] = {stripes_, stripe_rows_};
         std::memcpy(h.data() + kMoveHeader, st, sizeof st);
     }
-    std::memcpy(h.data() + tgt, b.targets.data(), 4ull * nrows_);
+    if (nrows_) std::memcpy(h.data() + tgt, b.targets.data(), 4ull * nrows_);
     try {
         pwrite_all(fd_, h.data(), h.size(), 0);
         for (uint32_t j = 0; striped && j < stripes_; ++j) {
@@ -753,10 +785,9 @@ void MoveBucketFile::close(uint64_t total_runs) {
 }
 
 MoveBucket read_move_bucket_head(const std::string& path, bool check_parts) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    std::ifstream f(path, std::ios::binary);
     if (!f) throw Error(CPD_E_IO, "cannot open " + path);
-    const uint64_t size = (uint64_t)f.tellg();
-    f.seekg(0);
+    const uint64_t size = stream_size(f);
     char magic[8];
     f.read(magic, 8);
     const bool striped = f && std::memcmp(magic, kMoveStripedMagic, 8) == 0;
@@ -787,10 +818,14 @@ MoveBucket read_move_bucket_head(const std::string& path, bool check_parts) {
         throw Error(CPD_E_IO, path + ": row width does not match n and bits per move");
     if (striped && (b.stripes < 2 || b.stripes > kMaxStripes || b.stripe_rows == 0))
         throw Error(CPD_E_IO, path + ": bad stripe layout");
+    // the size against the header before anything is sized by the header
+    const uint64_t head_end = (striped ? kStripedHeader : kMoveHeader) + 8ull * nrows;
+    const uint64_t rows_at = (head_end + kMoveRowsAlign - 1) / kMoveRowsAlign * kMoveRowsAlign;
+    if (size != (striped ? head_end : rows_at + 4ull * b.words * nrows))
+        throw Error(CPD_E_IO, path + ": size does not match its header");
     b.targets.resize(nrows);
     b.counts.resize(nrows);
     if (striped) {
-        if (size != b.head_bytes()) throw Error(CPD_E_IO, path + ": size does not match its header");
         for (uint32_t j = 0; check_parts && j < b.stripes; ++j) {
             const std::string pp = move_part_path(path, b.fingerprint, j);
             struct stat st {};
@@ -805,8 +840,6 @@ MoveBucket read_move_bucket_head(const std::string& path, bool check_parts) {
             if ((uint64_t)st.st_size != b.part_rows(j) * 4ull * b.words)
                 throw Error(CPD_E_IO, pp + ": size does not match its bucket");
         }
-    } else if (size != b.rows_offset() + 4ull * b.words * nrows) {
-        throw Error(CPD_E_IO, path + ": size does not match its header");
     }
     f.read(reinterpret_cast<char*>(b.targets.data()), nrows * 4ull);
     f.read(reinterpret_cast<char*>(b.counts.data()), nrows * 4ull);
@@ -918,6 +951,7 @@ uint32_t read_order_n(const std::string& path) {
 std::vector<uint32_t> read_order(const std::string& path, uint64_t fp) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw Error(CPD_E_IO, "cannot open " + path);
+    const uint64_t size = stream_size(f);
     char magic[8];
     uint32_t n = 0;
     uint64_t got = 0;
@@ -926,6 +960,7 @@ std::vector<uint32_t> read_order(const std::string& path, uint64_t fp) {
     f.read(reinterpret_cast<char*>(&got), 8);
     if (!f || std::memcmp(magic, kOrderMagic, 8) != 0) throw Error(CPD_E_IO, path + ": not an order file");
     if (got != fp) throw Error(CPD_E_IO, path + ": built for a different graph");
+    if (size != 20 + 4ull * n) throw Error(CPD_E_IO, path + ": size does not match its header");
     std::vector<uint32_t> order(n);
     f.read(reinterpret_cast<char*>(order.data()), n * 4ull);
     if (!f) throw Error(CPD_E_IO, path + ": truncated");

@@ -5,7 +5,16 @@
 //          "v id x y" and "e from to cost" lines.  Out-edge k of a node is its
 //          k-th "e" line (file order) [U: warthog xy_graph].
 //   .diff  congested weights: "e from to cost" (or "from to cost") lines, each
-//          replacing the weight of the first from->to edge [U].
+//          replacing the weight of the first from->to edge [U].  A line cannot
+//          name the second of two parallel edges, so write_diff -> read_diff
+//          is the identity only on graphs without parallel edges: weights
+//          [5, 6] -> [5, 9] on two 0->1 edges are written "e 0 1 9" and read
+//          back as [9, 6] (pinned in tests/test_io_cpu.py).
+//   Every numeric field of the text formats is range-checked (ids, costs and
+//   counts in u32, coordinates in int32, at most 2^28 - 1 nodes): a value
+//   outside is CPD_E_IO naming the file and line, never a wrapped value.  The
+//   binary readers check the file's size against its header before they size
+//   anything by a header field.
 //   .scen  scenario: "q s t" lines (process_query.read_p2p, :22-32).
 //   query  "{n}\n" then n lines "s t" (process_query.send_queries, :93-96).
 //   .cpd   one file per partition bucket (README.md:86-93 "one or more CPDs"),
@@ -64,6 +73,11 @@ std::string bucket_path(const std::string& outdir, const std::string& xy_path,
                         const std::string& method, uint32_t key, uint32_t bid);
 std::string order_path(const std::string& outdir, const std::string& xy_path);
 
+// DOSCPD01 — run words (all fields little-endian, no padding):
+//   magic "DOSCPD01" | n nrows bid method key maxworker (6 x u32) |
+//   total u64 | fingerprint u64 | targets u32[nrows] |
+//   offsets u64[nrows + 1] (offsets[0] = 0, offsets[nrows] = total) |
+//   runs u32[total]
 void write_bucket(const std::string& path, const CpdBucket& b);
 
 // A bucket file written in pieces, from several threads and in any order:
@@ -108,6 +122,9 @@ int bucket_format(const std::string& path);
 //   total_runs u64 | fingerprint u64 | targets u32[nrows] |
 //   runs u32[nrows] (run count of each row) | zero pad to a 4-KiB boundary |
 //   rows u32[nrows][words], words = ceil(n * bits / 32)
+// DOSCPD03: magic "DOSCPD03" | the same 8 x u32, total_runs, fingerprint |
+//   stripes u32 | stripe_rows u32 | targets u32[nrows] | runs u32[nrows], no
+//   pad; the rows in the part files (below), each part's rows back to back.
 struct MoveBucket {
     uint32_t n = 0, bid = 0, method = 0, key = 0, maxworker = 0, words = 0, bits = 4;
     uint64_t fingerprint = 0, total_runs = 0;
@@ -154,6 +171,7 @@ MoveBucket read_move_bucket_head(const std::string& path, bool check_parts = tru
 void read_move_bucket_rows(const std::string& path, const MoveBucket& head, uint32_t first,
                            uint32_t count, uint32_t* out, int threads = 1);
 
+// .order: magic "DOSORD01" | n u32 | fingerprint u64 | order u32[n]
 void write_order(const std::string& path, uint64_t fingerprint, const std::vector<uint32_t>& order);
 std::vector<uint32_t> read_order(const std::string& path, uint64_t fingerprint);
 uint32_t read_order_n(const std::string& path);  // its node count (header only)

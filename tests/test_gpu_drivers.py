@@ -13,6 +13,7 @@ import pytest
 
 import cpd
 import driver_harness as H
+from bucket_files import read_bucket as _read_bucket, read_move_bucket as _read_move_bucket
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -108,58 +109,6 @@ def test_drivers_end_to_end(tmp_path, method, key, fmt):
             fifo = f"/tmp/worker{wid}.fifo"
             if os.path.exists(fifo):
                 os.remove(fifo)
-
-
-def _read_bucket(path):
-    """The bucket layout of csrc/cpd_io.cpp (write_bucket / BucketFile)."""
-    raw = open(path, "rb").read()
-    assert raw[:8] == b"DOSCPD01"
-    n, nrows, bid, method, key, maxworker = np.frombuffer(raw, np.uint32, 6, 8)
-    total = int(np.frombuffer(raw, np.uint64, 1, 32)[0])
-    p = 48
-    targets = np.frombuffer(raw, np.uint32, nrows, p)
-    p += 4 * int(nrows)
-    off = np.frombuffer(raw, np.uint64, nrows + 1, p)
-    p += 8 * (int(nrows) + 1)
-    runs = np.frombuffer(raw, np.uint32, total, p)
-    assert p + 4 * total == len(raw)
-    return targets, off, runs
-
-
-def _read_move_bucket(path):
-    """The compact bucket layouts of csrc/cpd_io.cpp (MoveBucketFile): DOSCPD02
-    (rows after the header) or DOSCPD03 (rows striped over part files
-    {path}.{fingerprint:016x}.p{j}: unit u of stripe_rows rows is unit u // K of
-    part u % K)."""
-    raw = open(path, "rb").read()
-    assert raw[:8] in (b"DOSCPD02", b"DOSCPD03")
-    n, nrows, bid, method, key, maxworker, words, bits = (int(x) for x in np.frombuffer(raw, np.uint32, 8, 8))
-    assert bits in (1, 2, 4) and words == (n * bits + 31) // 32
-    total = int(np.frombuffer(raw, np.uint64, 1, 40)[0])
-    if raw[:8] == b"DOSCPD02":
-        p = 56
-        targets = np.frombuffer(raw, np.uint32, nrows, p)
-        counts = np.frombuffer(raw, np.uint32, nrows, p + 4 * nrows)
-        rows_at = -(-(p + 8 * nrows) // 4096) * 4096
-        assert len(raw) == rows_at + 4 * words * nrows
-        moves = np.frombuffer(raw, np.uint32, nrows * words, rows_at).reshape(nrows, words)
-    else:
-        K, S = (int(x) for x in np.frombuffer(raw, np.uint32, 2, 56))
-        p = 64
-        targets = np.frombuffer(raw, np.uint32, nrows, p)
-        counts = np.frombuffer(raw, np.uint32, nrows, p + 4 * nrows)
-        assert len(raw) == p + 8 * nrows
-        fp = int(np.frombuffer(raw, np.uint64, 1, 48)[0])
-        parts = [np.fromfile(f"{path}.{fp:016x}.p{j}", np.uint32).reshape(-1, words)
-                 for j in range(K)]
-        moves = np.empty((nrows, words), np.uint32)
-        for u in range(-(-nrows // S)):
-            r0, r1 = u * S, min(nrows, u * S + S)
-            q = (u // K) * S
-            moves[r0:r1] = parts[u % K][q:q + (r1 - r0)]
-        assert sum(len(x) for x in parts) == nrows
-    assert int(counts.sum()) == total
-    return targets, counts, moves, bits
 
 
 @pytest.mark.parametrize("fmt", ["moves", "moves1", "rle"])
