@@ -41,6 +41,8 @@ TIMED_LOADS = 2
 STEP_LINE = 0xFFFFFFFF
 ALPHA_CONJ = 0xFFFFFFFF
 ALPHA_MAX = 64881
+BI_AUTO = 0xFFFFFFFF
+BI_MAX = (1 << 23) - 1
 
 EXPORTED = [
     "cpd_last_error", "cpd_version", "cpd_partition", "cpd_partition_nbuckets",
@@ -70,7 +72,11 @@ EXPORTED = [
     "cpd_query_assign",
     "cpd_index_flow_step", "cpd_index_flow_fetch", "cpd_index_flow_clear", "cpd_query_assign_line",
     "cpd_index_flow_step_conj", "cpd_index_target_fetch", "cpd_query_assign_conj",
+    "cpd_index_flow_step_bi", "cpd_query_assign_bi",
 ]
+# entry points with a digit in the name, listed apart: EXPORTED is compared with
+# a scan of the header for names of letters and underscores
+EXPORTED_MORE = ["cpd_index_target2_fetch"]
 # generator styles (cpd_synth_road_graph_ex flags): "shuffled" is round 1's
 # graph (ids permuted, one-way streets, out-edge order shuffled); "spec" is
 # SURVEY.md §8(d) as written (row-major ids, bidirectional, E/N/W/S order)
@@ -171,6 +177,24 @@ class AssignConjIter(C.Structure):
                [(k, C.c_uint64) for k in ("n_lo", "n_hi", "m_lo", "m_hi", "gy_lo", "gy_hi")]
 
 
+class BiInfo(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("branch", "mu_q16", "nu_q16", "beta0_q16", "beta1_q16",
+                                          "beta2_q16", "alpha_q16", "lambda_prev_q16",
+                                          "lambda_q16", "evals")] + \
+               [(k, C.c_uint64) for k in ("a1_lo", "a1_hi", "b1_lo", "b1_hi", "a2_lo", "a2_hi",
+                                          "b2_lo", "b2_hi", "gy_lo", "gy_hi", "xw0_lo", "xw0_hi",
+                                          "g0_lo", "g0_hi", "tstt_lo", "tstt_hi", "changed")] + \
+               [("bi_ms", C.c_double), ("line_ms", C.c_double), ("apply_ms", C.c_double)]
+
+
+class AssignBiIter(C.Structure):
+    _fields_ = AssignLineIter._fields_ + \
+               [(k, C.c_uint32) for k in ("branch", "mu_q16", "nu_q16", "beta0_q16", "beta1_q16",
+                                          "beta2_q16", "alpha_q16")] + \
+               [(k, C.c_uint64) for k in ("a1_lo", "a1_hi", "b1_lo", "b1_hi", "a2_lo", "a2_hi",
+                                          "b2_lo", "b2_hi", "gy_lo", "gy_hi")]
+
+
 def _u128(lo: int, hi: int) -> int:
     """An unsigned 128-bit value from its two u64 halves."""
     return (hi << 64) | lo
@@ -192,12 +216,17 @@ _ITER_KEYS = (("finished", "plain"), ("sptt", "u128"), ("tstt", "u128"), ("moves
               ("xw0", "u128"), ("line_ms", "plain"), ("alpha_q16", "plain"), ("n", "s128"),
               ("m", "u128"), ("gy", "s128"))
 _ITER_NKEYS = {AssignIter: 8, AssignLineIter: 13, AssignConjIter: 17}  # the leading keys a type holds
+# cpd_assign_bi_iter: cpd_assign_line_iter's keys, then its own
+_BI_KEYS = _ITER_KEYS[:13] + tuple((k, "plain") for k in ("branch", "mu_q16", "nu_q16", "beta0_q16",
+                                                          "beta1_q16", "beta2_q16", "alpha_q16")) + \
+    (("a1", "s128"), ("b1", "u128"), ("a2", "s128"), ("b2", "s128"), ("gy", "s128"))
 
 
 def _iter_dict(r) -> dict:
     """One record of an assignment loop as a dict."""
     d = {}
-    for key, kind in _ITER_KEYS[:_ITER_NKEYS[type(r)]]:
+    keys = _BI_KEYS if type(r) is AssignBiIter else _ITER_KEYS[:_ITER_NKEYS[type(r)]]
+    for key, kind in keys:
         if kind == "plain":
             d[key] = getattr(r, key)
         else:
@@ -218,7 +247,7 @@ def _load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     lib.cpd_last_error.restype = C.c_char_p
     lib.cpd_version.restype = C.c_char_p
-    for name in EXPORTED:
+    for name in EXPORTED + EXPORTED_MORE:
         if name not in ("cpd_last_error", "cpd_version"):
             fn = getattr(lib, name)
             if not name.endswith("_free"):
@@ -1251,6 +1280,64 @@ class Index:
         """cpd_query_assign_conj on the prepared queries (capacity_cols as in
         assign_run)."""
         return self._assign_loop(lib.cpd_query_assign_conj, AssignConjIter, True,
+                                 (CPD_E_OOM, CPD_E_RANGE), capacity, iters, demand, a, power,
+                                 prefix_bytes,
+                                 (hscale, fscale, k_moves, itrs, time_ns, capacity_cols,
+                                  virtual_tick_ns, tables, workspace_frac, capacity_max))
+
+    @staticmethod
+    def _bi(v) -> int:
+        return BI_AUTO if v == "auto" else int(v) & 0xFFFFFFFF
+
+    def flow_step_bi(self, capacity, mu="auto", nu="auto", lam="line", a=(3, 20),
+                     power: int = 4) -> dict:
+        """One bi-conjugate step towards the resident one-plane load table
+        (cpd_index_flow_step_bi, cpd_api.h "The bi-conjugate step"): mu and nu
+        = "auto" for the rules or values in 0..BI_MAX (Q16), lam as
+        flow_step's.  Returns branch, mu_q16, nu_q16, beta0_q16..beta2_q16,
+        alpha_q16, lambda_prev_q16, lambda_q16, evals, a1, a2, b2, gy and g0
+        (signed Python ints), b1, xw0 and tstt (Python ints), changed, bi_ms,
+        line_ms, apply_ms; the relative gap before the step is -gy / xw0."""
+        c = self._capacity(capacity)
+        f = Vdf(int(a[0]), int(a[1]), int(power), 1)
+        info = BiInfo()
+        _check(lib.cpd_index_flow_step_bi(self._h, _ptr(c, u32p), C.byref(f),
+                                          C.c_uint32(self._bi(mu)), C.c_uint32(self._bi(nu)),
+                                          C.c_uint32(self._lambda(lam)), C.byref(info)))
+        d = {k: getattr(info, k) for k in ("branch", "mu_q16", "nu_q16", "beta0_q16", "beta1_q16",
+                                           "beta2_q16", "alpha_q16", "lambda_prev_q16",
+                                           "lambda_q16", "evals", "changed", "bi_ms", "line_ms",
+                                           "apply_ms")}
+        for k in ("a1", "a2", "b2", "gy", "g0"):
+            d[k] = _s128(getattr(info, k + "_lo"), getattr(info, k + "_hi"))
+        for k in ("b1", "xw0", "tstt"):
+            d[k] = _u128(getattr(info, k + "_lo"), getattr(info, k + "_hi"))
+        return d
+
+    def target2_fetch(self) -> np.ndarray:
+        """The second target table, u64[m] in original edge order, Q16
+        (cpd_index_target2_fetch): the target before target_fetch()'s."""
+        x = np.empty(self.graph.plan.info()["m"], np.uint64)
+        _check(lib.cpd_index_target2_fetch(self._h, _ptr(x, u64p)))
+        return x
+
+    def assign_bi(self, s, t, capacity, iters: int, demand=None, a=(3, 20), power: int = 4,
+                  **search_opts):
+        """assign_conj() with the bi-conjugate step (cpd_query_assign_bi): one
+        dict per iteration made, holding assign_line()'s keys (g0 along S1 - X)
+        and branch, mu_q16, nu_q16, beta0_q16..beta2_q16, alpha_q16, a1, b1,
+        a2, b2, gy; the gap before step k is -gy / xw0.  Afterwards
+        target_fetch() and target2_fetch() return the last two targets."""
+        self.prepare(s, t)
+        return self.assign_bi_run(capacity, iters, demand, a, power, **search_opts)
+
+    def assign_bi_run(self, capacity, iters: int, demand=None, a=(3, 20), power: int = 4,
+                      prefix_bytes=0, hscale=1.0, fscale=0.0, k_moves=-1, itrs=-1, time_ns=0,
+                      capacity_cols=0, virtual_tick_ns=0, tables="auto", workspace_frac=0.0,
+                      capacity_max=0):
+        """cpd_query_assign_bi on the prepared queries (capacity_cols as in
+        assign_run)."""
+        return self._assign_loop(lib.cpd_query_assign_bi, AssignBiIter, True,
                                  (CPD_E_OOM, CPD_E_RANGE), capacity, iters, demand, a, power,
                                  prefix_bytes,
                                  (hscale, fscale, k_moves, itrs, time_ns, capacity_cols,

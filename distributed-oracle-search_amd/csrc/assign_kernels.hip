@@ -456,6 +456,159 @@ __global__ __launch_bounds__(256) void conj_target(const unsigned long long* __r
     }
 }
 
+// --- the bi-conjugate step (cpd_api.h "The bi-conjugate step") --------------
+
+// The step's six sums and the largest counter of Y: a lane per slot,
+// grid-stride, 44 bytes read per slot.  Slots with d1 == 0 and d2 == 0 skip the
+// slope.
+__global__ __launch_bounds__(256) void bi_sums(const unsigned long long* __restrict__ Y,
+                                               const unsigned long long* __restrict__ X,
+                                               const unsigned long long* __restrict__ S1,
+                                               const unsigned long long* __restrict__ S2,
+                                               const uint2* __restrict__ adj_free,
+                                               const uint32_t* __restrict__ cap_slot,
+                                               unsigned long long nslots, cpd_vdf f,
+                                               unsigned long long lp,
+                                               unsigned long long* __restrict__ st) {
+    U128 a1{0ull, 0ull}, b1{0ull, 0ull}, a2{0ull, 0ull}, b2{0ull, 0ull}, gy{0ull, 0ull},
+        xw{0ull, 0ull};
+    unsigned long long ymax = 0;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < nslots; i += step) {
+        const unsigned long long y = Y[i], x = X[i], s1 = S1[i], s2 = S2[i];
+        if (y > ymax) ymax = y;
+        if ((y | x | s1 | s2) == 0ull) continue;
+        const uint2 a = adj_free[i];
+        if (a.x == 0xFFFFFFFFu) continue;  // padding: all four tables are 0 there anyway
+        const uint32_t c = cap_slot[i];
+        // wraps for a counter the range check refuses: the sums are then unused
+        const long long dy = (long long)((y << 16) - x);
+        const long long d1 = (long long)(s1 - x) >> 16, df = dy >> 16;  // arithmetic: the floor
+        const long long d2 = (long long)(lp * s1 + (65536ull - lp) * s2 - (x << 16)) >> 32;
+        const long long e21 = (long long)(s2 - s1) >> 16;
+        if (d1 | d2) {
+            const unsigned long long h = vdf_slope(a.y, x >> 16, c, f);
+            if (d1) {
+                mad128_pqh(a1, d1, df, h);
+                mad128_pqh(b1, d1, d1, h);
+            }
+            if (d2) {
+                mad128_pqh(a2, d2, df, h);
+                mad128_pqh(b2, d2, e21, h);
+            }
+        }
+        const uint32_t w = vdf_weight(a.y, x >> 16, c, f);
+        mad128_signed(gy, dy, w);
+        mad128(xw, x, w);
+    }
+    wave_sum128(a1, 0ull, st + kConjN);
+    wave_sum128(b1, 0ull, st + kConjM);
+    wave_sum128(a2, 0ull, st + kBiA2);
+    wave_sum128(b2, 0ull, st + kBiB2);
+    wave_sum128(gy, 0ull, st + kConjGy);
+    wave_sum128(xw, 0ull, st + kFlowXw);
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long o = __shfl_down(ymax, d, 64);
+        ymax = o > ymax ? o : ymax;
+    }
+    if ((threadIdx.x & 63u) == 0u && ymax) atomicMax(&st[kFlowMaxY], ymax);
+}
+
+// min(floor(a * 65536 / b), CPD_BI_MAX) for magnitudes a, b < 2^124, b != 0.
+// The quotient reaches 2^23 exactly when a >= 128 b, that is (a >> 7) >= b;
+// below that it is made bit by bit from the top bit of a down through 16
+// fraction bits: the remainder stays below b, so doubled it is below 2^125.
+__device__ __forceinline__ unsigned long long quot_q16(const U128& a, const U128& b) {
+    const U128 a7{(a.lo >> 7) | (a.hi << 57), a.hi >> 7};
+    if (ge128(a7, b)) return CPD_BI_MAX;
+    const int top = a.hi ? 128 - __clzll((long long)a.hi) : a.lo ? 64 - __clzll((long long)a.lo) : 0;
+    U128 rem{0ull, 0ull};
+    unsigned long long q = 0;
+    for (int i = top + 15; i >= 0; --i) {
+        const int k = i - 16;  // the bit of a that comes down, none in the fraction
+        const unsigned long long bit = k < 0 ? 0ull : k >= 64 ? (a.hi >> (k - 64)) & 1ull
+                                                             : (a.lo >> k) & 1ull;
+        rem.hi = (rem.hi << 1) | (rem.lo >> 63);
+        rem.lo = (rem.lo << 1) | bit;
+        q <<= 1;
+        if (ge128(rem, b)) {
+            rem = sub128(rem, b);
+            q |= 1ull;
+        }
+    }
+    return q;
+}
+
+// One lane: refuses the step (st[kFlowDone] = 2) for a counter of Y at or
+// above 2^30, else mu and nu from the sums by the header's rules (want ==
+// CPD_BI_AUTO) or the caller's, and the three betas.  Plain stores from lane 0.
+__global__ __launch_bounds__(64) void bi_decide(uint32_t want_mu, uint32_t want_nu,
+                                                unsigned long long lp,
+                                                unsigned long long* __restrict__ st) {
+    if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+    if (st[kFlowMaxY] >= (1ull << 30)) {
+        st[kFlowDone] = 2ull;  // refused: nothing is written
+        return;
+    }
+    unsigned long long mu = want_mu, nu = want_nu;
+    if (want_mu == CPD_BI_AUTO) {
+        U128 a2{st[kBiA2], st[kBiA2 + 1]}, b2{st[kBiB2], st[kBiB2 + 1]};
+        const bool aneg = (long long)a2.hi < 0, bneg = (long long)b2.hi < 0;
+        mu = 0ull;
+        if ((a2.lo | a2.hi) != 0ull && (b2.lo | b2.hi) != 0ull && aneg != bneg)
+            mu = quot_q16(aneg ? neg128(a2) : a2, bneg ? neg128(b2) : b2);
+    }
+    if (want_nu == CPD_BI_AUTO) {
+        const U128 a1{st[kConjN], st[kConjN + 1]}, b1{st[kConjM], st[kConjM + 1]};
+        nu = 0ull;
+        if ((b1.lo | b1.hi) != 0ull && (long long)a1.hi < 0) nu = quot_q16(neg128(a1), b1);
+        nu += mu * lp / (65536ull - lp);  // mu < 2^23, lp < 2^16
+        if (nu > CPD_BI_MAX) nu = CPD_BI_MAX;
+    }
+    const unsigned long long beta0 = (1ull << 32) / (65536ull + mu + nu);
+    const unsigned long long beta2 = (mu * beta0) >> 16;
+    st[kBiMu] = mu;
+    st[kBiNu] = nu;
+    st[kBiBeta0] = beta0;
+    st[kBiBeta1] = 65536ull - beta0 - beta2;
+    st[kBiBeta2] = beta2;
+}
+
+// S2 <- the old target, S1 <- the new one on every slot once the decision has
+// accepted the range (see launch_bi_target).  BETA: the three-term sum is kept
+// in two halves (each product is below 2^81) and shifted down once.  Padding
+// slots hold 0 in every table and get 0.
+template <bool BETA>
+__global__ __launch_bounds__(256) void bi_target(const unsigned long long* __restrict__ Y,
+                                                 const unsigned long long* __restrict__ X,
+                                                 unsigned long long* __restrict__ S1,
+                                                 unsigned long long* __restrict__ S2,
+                                                 unsigned long long nslots, uint32_t has_s1,
+                                                 const unsigned long long* __restrict__ st) {
+    if (st[kFlowDone] != 0ull) return;
+    const unsigned long long alpha = st[kConjAlpha];
+    const unsigned long long beta0 = st[kBiBeta0], beta1 = st[kBiBeta1], beta2 = st[kBiBeta2];
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < nslots; i += step) {
+        const unsigned long long yq = Y[i] << 16;
+        if constexpr (BETA) {
+            const unsigned long long s1 = S1[i], s2 = S2[i];
+            U128 t{0ull, 0ull};
+            mad128(t, yq, beta0);
+            mad128(t, s1, beta1);
+            mad128(t, s2, beta2);
+            S2[i] = s1;
+            S1[i] = (t.lo >> 16) | (t.hi << 48);
+        } else {
+            const unsigned long long so = has_s1 ? S1[i] : X[i];
+            S2[i] = so;
+            S1[i] = flow_at(yq, (long long)(so - yq), alpha);
+        }
+    }
+}
+
 }  // namespace kern
 
 namespace {
@@ -566,6 +719,39 @@ void launch_conj_target(const uint64_t* Y, const uint64_t* X, const uint64_t* S_
                        reinterpret_cast<const unsigned long long*>(X),
                        reinterpret_cast<const unsigned long long*>(S_old),
                        reinterpret_cast<unsigned long long*>(S), nslots, st);
+}
+
+void launch_bi_sums(const uint64_t* Y, const uint64_t* X, const uint64_t* S1, const uint64_t* S2,
+                    const uint32_t* adj_free, const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f,
+                    uint32_t lp, unsigned long long* st, hipStream_t s) {
+    hipLaunchKernelGGL(kern::bi_sums, dim3(stride_grid(nslots)), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long*>(Y),
+                       reinterpret_cast<const unsigned long long*>(X),
+                       reinterpret_cast<const unsigned long long*>(S1),
+                       reinterpret_cast<const unsigned long long*>(S2),
+                       reinterpret_cast<const uint2*>(adj_free), cap_slot, nslots, f,
+                       (unsigned long long)lp, st);
+}
+
+void launch_bi_decide(uint32_t want_mu, uint32_t want_nu, uint32_t lp, unsigned long long* st,
+                      hipStream_t s) {
+    hipLaunchKernelGGL(kern::bi_decide, dim3(1), dim3(64), 0, s, want_mu, want_nu,
+                       (unsigned long long)lp, st);
+}
+
+void launch_bi_target(const uint64_t* Y, const uint64_t* X, uint64_t* S1, uint64_t* S2,
+                      uint64_t nslots, bool beta, bool has_s1, const unsigned long long* st,
+                      hipStream_t s) {
+    const auto* y = reinterpret_cast<const unsigned long long*>(Y);
+    const auto* x = reinterpret_cast<const unsigned long long*>(X);
+    auto* s1 = reinterpret_cast<unsigned long long*>(S1);
+    auto* s2 = reinterpret_cast<unsigned long long*>(S2);
+    const dim3 grid(stride_grid(nslots)), blk(256);
+    if (beta)
+        hipLaunchKernelGGL(kern::bi_target<true>, grid, blk, 0, s, y, x, s1, s2, nslots, 1u, st);
+    else
+        hipLaunchKernelGGL(kern::bi_target<false>, grid, blk, 0, s, y, x, s1, s2, nslots,
+                           has_s1 ? 1u : 0u, st);
 }
 
 }  // namespace cpd

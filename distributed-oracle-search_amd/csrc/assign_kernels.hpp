@@ -1,8 +1,8 @@
 // Host-callable launchers for the gfx950 kernels in assign_kernels.hip: the
 // slot-wise step from edge loads to weights (cpd_index_weights_from_loads),
 // the weights' way back to edge order (cpd_index_get_weights / _weight_sets)
-// the demand-weighted cost sum of a search (cpd_query_assign), the flow step
-// and the conjugate step.
+// the demand-weighted cost sum of a search (cpd_query_assign), the flow step,
+// the conjugate step and the bi-conjugate step.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
@@ -72,7 +72,17 @@ enum : uint32_t {
     kConjM = 21,      // +0, +1: M (unsigned 128), +2 unused
     kConjGy = 24,     // +0, +1: gy (signed 128), +2 unused
     kConjAlpha = 27,  // the alpha decided
-    kConjWords = 28
+    kConjWords = 28,
+    // the bi-conjugate step's words follow (A1, B1 and gy take kConjN, kConjM
+    // and kConjGy; a branch-1 step leaves the words below 0)
+    kBiA2 = 28,       // +0, +1: A2 (signed 128), +2 unused
+    kBiB2 = 31,       // +0, +1: B2 (signed 128), +2 unused
+    kBiMu = 34,       // the mu and nu decided
+    kBiNu = 35,
+    kBiBeta0 = 36,    // the weights of Yq, S1 and S2 in the new target, Q16
+    kBiBeta1 = 37,
+    kBiBeta2 = 38,
+    kBiWords = 39
 };
 // launch_flow_line_eval: st[kFlowG ..] += the sum over the real slots of D *
 // w(lambda), D = (Y << 16) - X, lambda = st[kFlowLambda]; `first` (the lambda
@@ -114,5 +124,31 @@ void launch_conj_sums(const uint64_t* Y, const uint64_t* X, const uint64_t* S,
 void launch_conj_decide(uint32_t want, unsigned long long* st, hipStream_t s);
 void launch_conj_target(const uint64_t* Y, const uint64_t* X, const uint64_t* S_old, uint64_t* S,
                         uint64_t nslots, const unsigned long long* st, hipStream_t s);
+
+// The bi-conjugate step (cpd_api.h "The bi-conjugate step"), over the same
+// state array grown to kBiWords.  Branch 2 queues the three launches below in
+// front of the line search's pairs; branch 1 queues launch_conj_sums and
+// launch_conj_decide and then launch_bi_target with beta == false.
+// launch_bi_sums: st[kConjN ..] += A1, st[kConjM ..] += B1, st[kBiA2 ..] += A2,
+// st[kBiB2 ..] += B2, st[kConjGy ..] += gy, st[kFlowXw ..] += xw0 over the real
+// slots, st[kFlowMaxY] = the largest counter of Y, in one pass.  S1, S2: the
+// two target tables (nslots u64, Q16); lp: lambda_prev, below 65536.
+// launch_bi_decide: one lane; a counter >= 2^30 sets st[kFlowDone] = 2 (every
+// later kernel of the step then does nothing), else st[kBiMu], st[kBiNu] = the
+// header's rules over the sums (want == CPD_BI_AUTO) or want itself, and
+// st[kBiBeta0 .. kBiBeta2] from them.
+// launch_bi_target: with st[kFlowDone] == 0, per slot S2 <- the old target and
+// S1 <- the new one, in place.  beta: the old target is S1 and the new one
+// floor((beta0 * Yq + beta1 * S1 + beta2 * S2) / 2^16) with the betas of st;
+// else the conjugate step's: the old target is S1, or X when has_s1 is false,
+// and the new one Yq + floor(alpha * (old - Yq) / 2^16), alpha = st[kConjAlpha].
+void launch_bi_sums(const uint64_t* Y, const uint64_t* X, const uint64_t* S1, const uint64_t* S2,
+                    const uint32_t* adj_free, const uint32_t* cap_slot, uint64_t nslots, cpd_vdf f,
+                    uint32_t lp, unsigned long long* st, hipStream_t s);
+void launch_bi_decide(uint32_t want_mu, uint32_t want_nu, uint32_t lp, unsigned long long* st,
+                      hipStream_t s);
+void launch_bi_target(const uint64_t* Y, const uint64_t* X, uint64_t* S1, uint64_t* S2,
+                      uint64_t nslots, bool beta, bool has_s1, const unsigned long long* st,
+                      hipStream_t s);
 
 }  // namespace cpd

@@ -1,8 +1,9 @@
 // Loads to weights in HBM and the loops around it (cpd_index_weights_from_loads,
-// cpd_index_get_weights / _weight_sets; cpd_index_flow_step and _flow_step_conj
-// over one step routine; cpd_query_assign, _assign_line and _assign_conj over
-// one loop).
+// cpd_index_get_weights / _weight_sets; cpd_index_flow_step, _flow_step_conj
+// and _flow_step_bi over one step routine; cpd_query_assign, _assign_line,
+// _assign_conj and _assign_bi over one loop).
 #include <cstddef>
+#include <type_traits>
 
 #include "assign_kernels.hpp"
 #include "cpd_gpu_internal.hpp"
@@ -197,31 +198,52 @@ void fetch_slot_table(cpd_index* ix, const uint64_t* tab, DevBuf<uint64_t>& stag
                                  std::to_string(bits) + ")");
 }
 
-const char* step_name(bool conj) { return conj ? "conjugate step" : "flow step"; }
+// The three steps over the flow table.
+enum class Step { plain, conj, bi };
+const char* step_name(Step k) {
+    return k == Step::plain ? "flow step" : k == Step::conj ? "conjugate step" : "bi-conjugate step";
+}
 
 // One step over the resident one-plane table Y with the slot-order capacities
 // in place, everything queued at once; the host reads the state once,
 // afterwards.  The plain step (cpd_index_flow_step) is the line search's
 // evaluate / decide pairs and the apply pass towards Y; it moves X without
-// knowing S, so the target table goes.  The conjugate step
+// knowing S, so the target tables go.  The conjugate step
 // (cpd_index_flow_step_conj) puts the sums, the alpha decision and the target
 // pass in front and runs the same pairs and pass towards the target table S,
-// over the state array grown to kConjWords.  *info: a plain step leaves
-// alpha, the sums and conj_ms 0.
-void flow_step(cpd_index* ix, const cpd_vdf& f, bool conj, uint32_t alpha_q16, uint32_t lambda_q16,
-               cpd_conj_info* info) {
+// over the state array grown to kConjWords; it drops S2.  The bi-conjugate step
+// (cpd_index_flow_step_bi; a_q16 is nu, mu_q16 used by it alone) is the
+// conjugate step without a flow table (branch 0); without a usable S2 (branch
+// 1) the conjugate step whose target pass also keeps the old target in S2;
+// else (branch 2) its own sums, decision and target pass over kBiWords.
+// *info: a1 and b1 are the conjugate step's N and M, bi_ms its conj_ms; a
+// plain step leaves alpha, the sums and bi_ms 0.
+void flow_step(cpd_index* ix, const cpd_vdf& f, Step kind, uint32_t a_q16, uint32_t mu_q16,
+               uint32_t lambda_q16, cpd_bi_info* info) {
     cpd_graph* g = ix->g;
     hipStream_t s = g->stream;
     const uint64_t nslots = (uint64_t)g->n << g->adj_shift;
+    const bool conj = kind != Step::plain;
     // no flow table: X = 0 and lambda = 65536 give X = Y << 16 whatever lambda
     // says (conjugate: S = X and alpha = 0 as well, so X = S = Y << 16)
     const bool init = !ix->flow_ready;
     const bool has_s = conj && !init && ix->target_ready;
-    const uint32_t words = conj ? kConjWords : kFlowWords;
+    const uint32_t lp = ix->lambda_prev;
+    const uint32_t branch =
+        kind != Step::bi || init ? 0u : has_s && ix->target2_ready && lp != 65536u ? 2u : 1u;
+    uint32_t alpha_q16 = a_q16;
+    if (branch == 1u) {
+        CPD_REQUIRE(a_q16 == CPD_BI_AUTO || a_q16 == 0u, CPD_E_ARG,
+                    std::string(step_name(kind)) + ": nu_q16 " + std::to_string(a_q16) +
+                        " without a usable second target (branch 1 takes 0 or CPD_BI_AUTO)");
+        alpha_q16 = a_q16 == 0u ? 0u : CPD_ALPHA_CONJ;
+    }
+    const uint32_t words = kind == Step::bi ? kBiWords : conj ? kConjWords : kFlowWords;
     {
         ArenaScope carve;
         ix->fl_tab.alloc((size_t)nslots);
         if (conj) ix->tg_tab.alloc((size_t)nslots);
+        if (branch) ix->tg2_tab.alloc((size_t)nslots);
         ix->fl_st.alloc(words);
         ix->adj_sel.alloc((size_t)(2u * nslots));
     }
@@ -230,21 +252,34 @@ void flow_step(cpd_index* ix, const cpd_vdf& f, bool conj, uint32_t alpha_q16, u
     const uint32_t want = init ? 65536u : lambda_q16;
     const uint32_t pairs = want <= 65536u ? 1u : 18u;
     const uint64_t* towards = conj ? ix->tg_tab.p : ix->ld_tab.p;  // Q16 when conj
-    Events<4> ev(g);  // conjugate passes | line search | apply; e[0] is the conjugate step's alone
+    Events<4> ev(g);  // target passes | line search | apply; e[0] is not the plain step's
     (void)hipGetLastError();
-    if (conj) {
+    if (branch == 2u) {
+        HIP_CHECK(hipEventRecord(ev.e[0], s));
+        launch_bi_sums(ix->ld_tab.p, ix->fl_tab.p, ix->tg_tab.p, ix->tg2_tab.p, g->adj.p,
+                       ix->vdf_cap.p, nslots, f, lp, ix->fl_st.p, s);
+        launch_bi_decide(mu_q16, a_q16, lp, ix->fl_st.p, s);
+        launch_bi_target(ix->ld_tab.p, ix->fl_tab.p, ix->tg_tab.p, ix->tg2_tab.p, nslots, true,
+                         true, ix->fl_st.p, s);
+        HIP_CHECK(hipGetLastError());
+    } else if (conj) {
         const uint64_t* s_old = has_s ? ix->tg_tab.p : nullptr;
         HIP_CHECK(hipEventRecord(ev.e[0], s));
         launch_conj_sums(ix->ld_tab.p, ix->fl_tab.p, s_old, g->adj.p, ix->vdf_cap.p, nslots, f,
                          ix->fl_st.p, s);
         launch_conj_decide(init ? 0u : alpha_q16, ix->fl_st.p, s);
-        launch_conj_target(ix->ld_tab.p, ix->fl_tab.p, s_old, ix->tg_tab.p, nslots, ix->fl_st.p, s);
+        if (branch == 1u)
+            launch_bi_target(ix->ld_tab.p, ix->fl_tab.p, ix->tg_tab.p, ix->tg2_tab.p, nslots,
+                             false, has_s, ix->fl_st.p, s);
+        else
+            launch_conj_target(ix->ld_tab.p, ix->fl_tab.p, s_old, ix->tg_tab.p, nslots,
+                               ix->fl_st.p, s);
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipEventRecord(ev.e[1], s));
     for (uint32_t i = 0; i < pairs; ++i) {
         // `first` (the lambda = 0 pass also sums X * w(0) and takes the largest
-        // Y) is the plain step's: conj_sums has done both
+        // Y) is the plain step's: the sums passes have done both
         launch_flow_line_eval(towards, ix->fl_tab.p, g->adj.p, ix->vdf_cap.p, nslots, f,
                               !conj && i == 0u, ix->fl_st.p, s, conj);
         launch_flow_line_decide(want, ix->fl_st.p, s);
@@ -255,74 +290,140 @@ void flow_step(cpd_index* ix, const cpd_vdf& f, bool conj, uint32_t alpha_q16, u
                       ix->fl_st.p, s, conj);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ev.e[3], s));
-    // a plain step's alpha and sums read as 0: their words lie past the ones it copies
+    // a shorter step's later words read as 0: they lie past the ones it copies
     static_assert(kConjN >= kFlowWords && kConjAlpha >= kFlowWords, "conjugate words overlap");
-    unsigned long long h[kConjWords] = {};
+    static_assert(kBiA2 >= kConjWords && kBiBeta2 < kBiWords, "bi-conjugate words overlap");
+    unsigned long long h[kBiWords] = {};
     HIP_CHECK(hipMemcpyAsync(h, ix->fl_st.p, words * sizeof(unsigned long long),
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     // a counter at or above 2^47 (Y << 16 would pass 2^63) / 2^30 (the sums' terms)
-    if (h[kFlowDone] != 1ull) refuse_range(ix, step_name(conj), conj ? 30u : 47u);
+    if (h[kFlowDone] != 1ull) refuse_range(ix, step_name(kind), conj ? 30u : 47u);
     if (!conj) ix->tg_tab.release();  // the step moved X without knowing S
+    if (!branch) {  // ... or S1 without knowing S2
+        ix->tg2_tab.release();
+        ix->lambda_prev = 65536u;
+    }
+    if (kind == Step::bi) ix->lambda_prev = (uint32_t)h[kFlowLambda];
     ix->target_ready = conj;
+    ix->target2_ready = branch != 0u;
     ix->flow_ready = true;
     ix->custom_w = true;
     ix->c_ready = false;  // the search's incumbent tables follow the weights
-    float conj_ms = 0.f, line_ms = 0.f, apply_ms = 0.f;
-    if (conj) HIP_CHECK(hipEventElapsedTime(&conj_ms, ev.e[0], ev.e[1]));
+    float bi_ms = 0.f, line_ms = 0.f, apply_ms = 0.f;
+    if (conj) HIP_CHECK(hipEventElapsedTime(&bi_ms, ev.e[0], ev.e[1]));
     HIP_CHECK(hipEventElapsedTime(&line_ms, ev.e[1], ev.e[2]));
     HIP_CHECK(hipEventElapsedTime(&apply_ms, ev.e[2], ev.e[3]));
-    // the sums read Y, X, S, the free-flow pair and the capacity (36 B a slot),
-    // the target pass reads Y and S (or X) and writes S (24 B); per evaluation
-    // and slot: Y, X, the free-flow pair, the capacity (28 B); the apply also
+    // the conjugate sums read Y, X, S, the free-flow pair and the capacity (36 B
+    // a slot), the target pass reads Y and S (or X) and writes S (24 B); branch
+    // 1 also writes S2 (8 B); branch 2's sums read S2 as well (44 B) and its
+    // target pass reads Y, S1, S2 and writes S1, S2 (40 B); per evaluation and
+    // slot: Y, X, the free-flow pair, the capacity (28 B); the apply also
     // writes X and the selected pair
-    if (conj) add_agg(g, "conj_sums_target", 3, conj_ms, (double)nslots * 60.0);
+    if (kind == Step::bi)
+        add_agg(g, "bi_sums_target", 3, bi_ms,
+                (double)nslots * (branch == 2u ? 84.0 : branch == 1u ? 68.0 : 60.0));
+    else if (conj)
+        add_agg(g, "conj_sums_target", 3, bi_ms, (double)nslots * 60.0);
     add_agg(g, "flow_line_eval", h[kFlowEvals], line_ms,
             (double)nslots * 28.0 * (double)h[kFlowEvals]);
     add_agg(g, "flow_apply", 1, apply_ms, (double)nslots * 44.0);
-    *info = cpd_conj_info{};
+    *info = cpd_bi_info{};
+    info->branch = branch;
+    info->lambda_prev_q16 = lp;
     info->lambda_q16 = (uint32_t)h[kFlowLambda];
     if (!init) {  // the initialising step reports no evaluation and no sums
-        info->alpha_q16 = (uint32_t)h[kConjAlpha];
         info->evals = (uint32_t)h[kFlowEvals];
-        info->n_lo = h[kConjN];
-        info->n_hi = h[kConjN + 1];
-        info->m_lo = h[kConjM];
-        info->m_hi = h[kConjM + 1];
+        info->a1_lo = h[kConjN];
+        info->a1_hi = h[kConjN + 1];
+        info->b1_lo = h[kConjM];
+        info->b1_hi = h[kConjM + 1];
+        info->a2_lo = h[kBiA2];
+        info->a2_hi = h[kBiA2 + 1];
+        info->b2_lo = h[kBiB2];
+        info->b2_hi = h[kBiB2 + 1];
         info->gy_lo = h[kConjGy];
         info->gy_hi = h[kConjGy + 1];
         info->xw0_lo = h[kFlowXw];
         info->xw0_hi = h[kFlowXw + 1];
         info->g0_lo = h[kFlowG0];
         info->g0_hi = h[kFlowG0 + 1];
+        if (branch == 2u) {
+            info->mu_q16 = (uint32_t)h[kBiMu];
+            info->nu_q16 = (uint32_t)h[kBiNu];
+            info->beta0_q16 = (uint32_t)h[kBiBeta0];
+            info->beta1_q16 = (uint32_t)h[kBiBeta1];
+            info->beta2_q16 = (uint32_t)h[kBiBeta2];
+        } else {
+            info->alpha_q16 = (uint32_t)h[kConjAlpha];
+            if (branch == 1u) {  // the conjugate target in the bi-conjugate step's terms
+                info->beta0_q16 = 65536u - info->alpha_q16;
+                info->beta1_q16 = info->alpha_q16;
+            }
+        }
     }
     info->tstt_lo = h[kFlowTstt];
     info->tstt_hi = h[kFlowTstt + 1];
     info->changed = h[kFlowTstt + 2];
-    info->conj_ms = conj_ms;
+    info->bi_ms = bi_ms;
     info->line_ms = line_ms;
     info->apply_ms = apply_ms;
 }
 
-// cpd_index_flow_step / _flow_step_conj: the checks, the capacities, one step.
-void checked_step(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f, bool conj,
-                  uint32_t alpha_q16, uint32_t lambda_q16, cpd_conj_info* info) {
-    const char* who = step_name(conj);
+void check_bi(uint32_t v, const char* name, const char* who) {
+    CPD_REQUIRE(v <= CPD_BI_MAX || v == CPD_BI_AUTO, CPD_E_ARG,
+                std::string(who) + ": " + name + " " + std::to_string(v) +
+                    " is neither 0..8388607 nor CPD_BI_AUTO");
+}
+
+// cpd_index_flow_step / _flow_step_conj / _flow_step_bi: the checks, the
+// capacities, one step.
+void checked_step(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f, Step kind,
+                  uint32_t a_q16, uint32_t mu_q16, uint32_t lambda_q16, cpd_bi_info* info) {
+    const char* who = step_name(kind);
     CPD_REQUIRE(ix, CPD_E_ARG, std::string(who) + ": null index");
     check_vdf(f, false, who);
-    if (conj) check_alpha(alpha_q16, who);
+    if (kind == Step::conj) check_alpha(a_q16, who);
+    if (kind == Step::bi) {
+        check_bi(mu_q16, "mu_q16", who);
+        check_bi(a_q16, "nu_q16", who);
+    }
     check_lambda(lambda_q16, who);
     check_complete(ix, who);
     check_flow_table(ix, who);
     check_capacity(ix, capacity, who);
     ix->g->select();
     upload_capacity(ix, capacity);
-    flow_step(ix, *f, conj, alpha_q16, lambda_q16, info);
+    flow_step(ix, *f, kind, a_q16, mu_q16, lambda_q16, info);
 }
 
-// The three rules of the assignment loop.
-enum class Rule { msa, line, conj };
-const char* const kLoopName[] = {"assign", "assign line", "assign conj"};
+cpd_conj_info conj_info_of(const cpd_bi_info& b) {
+    cpd_conj_info c{};
+    c.alpha_q16 = b.alpha_q16;
+    c.lambda_q16 = b.lambda_q16;
+    c.evals = b.evals;
+    c.n_lo = b.a1_lo;
+    c.n_hi = b.a1_hi;
+    c.m_lo = b.b1_lo;
+    c.m_hi = b.b1_hi;
+    c.gy_lo = b.gy_lo;
+    c.gy_hi = b.gy_hi;
+    c.xw0_lo = b.xw0_lo;
+    c.xw0_hi = b.xw0_hi;
+    c.g0_lo = b.g0_lo;
+    c.g0_hi = b.g0_hi;
+    c.tstt_lo = b.tstt_lo;
+    c.tstt_hi = b.tstt_hi;
+    c.changed = b.changed;
+    c.conj_ms = b.bi_ms;
+    c.line_ms = b.line_ms;
+    c.apply_ms = b.apply_ms;
+    return c;
+}
+
+// The four rules of the assignment loop.
+enum class Rule { msa, line, conj, bi };
+const char* const kLoopName[] = {"assign", "assign line", "assign conj", "assign bi"};
 
 // An error of iteration k >= 2: the k - 1 before it stand.
 Error iteration_failed(int code, Rule rule, uint32_t k, uint32_t iters, const std::string& why) {
@@ -354,6 +455,8 @@ void loading_round(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_b
         if (reset_flow) {  // the loop starts from an empty flow table
             ix->flow_ready = false;
             ix->target_ready = false;
+            ix->target2_ready = false;
+            ix->lambda_prev = 65536u;
         }
         Events<2> ev(g);
         HIP_CHECK(hipEventRecord(ev.e[0], s));
@@ -396,17 +499,24 @@ SAME_PLACE(cpd_assign_line_iter, line_ms);
 static_assert(sizeof(cpd_assign_iter) == offsetof(cpd_assign_conj_iter, lambda_q16) &&
                   sizeof(cpd_assign_line_iter) == offsetof(cpd_assign_conj_iter, alpha_q16),
               "a shorter record ends where the next one's own fields begin");
+// cpd_assign_bi_iter has its own tail after cpd_assign_line_iter's fields
+static_assert(sizeof(cpd_assign_line_iter) == offsetof(cpd_assign_bi_iter, branch),
+              "the bi-conjugate record's tail begins where cpd_assign_line_iter ends");
 
-// cpd_query_assign, _assign_line and _assign_conj.  Every iteration: a loading
-// and sptt (loading_round), then the rule's update — MSA turns the summed
-// table over k into weights (apply_vdf; no flow state, no early stop, its
-// errors not wrapped), the other two take a line-search step, plain or
-// conjugate (flow_step).  done: null for MSA, which always makes `iters`.
+// cpd_query_assign, _assign_line, _assign_conj and _assign_bi.  Every
+// iteration: a loading and sptt (loading_round), then the rule's update — MSA
+// turns the summed table over k into weights (apply_vdf; no flow state, no
+// early stop, its errors not wrapped), the others take a line-search step,
+// plain, conjugate or bi-conjugate (flow_step).  The loop fills a
+// cpd_assign_conj_iter and the bi-conjugate step's info; the bi-conjugate
+// record takes the former's cpd_assign_line_iter part and its own tail from
+// the latter.  done: null for MSA, which always makes `iters`.
 template <class Rec>
 void assign_loop(Rule rule, cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
                  const uint32_t* demand, const uint32_t* capacity, const cpd_vdf* f, uint32_t iters,
                  Rec* out, uint32_t* done) {
-    static_assert(sizeof(Rec) <= sizeof(cpd_assign_conj_iter), "not a loop record");
+    constexpr bool bi_rec = std::is_same<Rec, cpd_assign_bi_iter>::value;
+    static_assert(bi_rec || sizeof(Rec) <= sizeof(cpd_assign_conj_iter), "not a loop record");
     const char* who = kLoopName[(int)rule];
     const bool msa = rule == Rule::msa;
     CPD_REQUIRE(ix && out && (done || msa), CPD_E_ARG, std::string(who) + ": null argument");
@@ -419,7 +529,7 @@ void assign_loop(Rule rule, cpd_index* ix, const cpd_search_opts* opts, uint64_t
     ix->g->select();
     const uint32_t nq = ix->nq;
     float cap_ms = 0.f;    // the capacity upload, in record 1
-    bool restart = false;  // the last conjugate direction went nowhere
+    bool restart = false;  // the last (bi-)conjugate direction went nowhere
     for (uint32_t k = 1; k <= iters; ++k) {
         cpd_search_stats ss{};
         cpd_search_loads_info li{};
@@ -427,6 +537,7 @@ void assign_loop(Rule rule, cpd_index* ix, const cpd_search_opts* opts, uint64_t
         loading_round(ix, opts, prefix_bytes, demand, capacity, rule, k, iters,
                       msa && k > 1 ? CPD_LOADS_ACCUMULATE : 0u, !msa, ss, li, h, cap_ms);
         cpd_assign_conj_iter r{};
+        cpd_bi_info ci{};
         if (msa) {
             cpd_vdf fk = *f;
             fk.load_div = k;
@@ -437,10 +548,13 @@ void assign_loop(Rule rule, cpd_index* ix, const cpd_search_opts* opts, uint64_t
             r.changed = vi.changed;
             r.vdf_ms = vi.vdf_ms;
         } else {
-            cpd_conj_info ci{};
             try {
-                flow_step(ix, *f, rule == Rule::conj, restart ? 0u : CPD_ALPHA_CONJ, CPD_STEP_LINE,
-                          &ci);
+                if (rule == Rule::bi)
+                    flow_step(ix, *f, Step::bi, restart ? 0u : CPD_BI_AUTO,
+                              restart ? 0u : CPD_BI_AUTO, CPD_STEP_LINE, &ci);
+                else
+                    flow_step(ix, *f, rule == Rule::conj ? Step::conj : Step::plain,
+                              restart ? 0u : CPD_ALPHA_CONJ, 0u, CPD_STEP_LINE, &ci);
             } catch (const Error& e) {
                 if (k == 1) throw;
                 throw iteration_failed(e.code, rule, k, iters, e.what());
@@ -455,12 +569,12 @@ void assign_loop(Rule rule, cpd_index* ix, const cpd_search_opts* opts, uint64_t
             r.g0_hi = ci.g0_hi;
             r.xw0_lo = ci.xw0_lo;
             r.xw0_hi = ci.xw0_hi;
-            r.line_ms = ci.conj_ms + ci.line_ms;
+            r.line_ms = ci.bi_ms + ci.line_ms;
             r.alpha_q16 = ci.alpha_q16;
-            r.n_lo = ci.n_lo;
-            r.n_hi = ci.n_hi;
-            r.m_lo = ci.m_lo;
-            r.m_hi = ci.m_hi;
+            r.n_lo = ci.a1_lo;
+            r.n_hi = ci.a1_hi;
+            r.m_lo = ci.b1_lo;
+            r.m_hi = ci.b1_hi;
             r.gy_lo = ci.gy_lo;
             r.gy_hi = ci.gy_hi;
         }
@@ -471,15 +585,39 @@ void assign_loop(Rule rule, cpd_index* ix, const cpd_search_opts* opts, uint64_t
         r.search_ms = ss.kernel_ms + ss.tables_ms;
         r.loads_ms = li.loads_ms;
         r.vdf_ms += k == 1 ? cap_ms : 0.f;
-        std::memcpy(&out[k - 1], &r, sizeof(Rec));
+        if constexpr (bi_rec) {
+            cpd_assign_bi_iter rb{};
+            std::memcpy(&rb, &r, sizeof(cpd_assign_line_iter));
+            rb.branch = ci.branch;
+            rb.mu_q16 = ci.mu_q16;
+            rb.nu_q16 = ci.nu_q16;
+            rb.beta0_q16 = ci.beta0_q16;
+            rb.beta1_q16 = ci.beta1_q16;
+            rb.beta2_q16 = ci.beta2_q16;
+            rb.alpha_q16 = ci.alpha_q16;
+            rb.a1_lo = ci.a1_lo;
+            rb.a1_hi = ci.a1_hi;
+            rb.b1_lo = ci.b1_lo;
+            rb.b1_hi = ci.b1_hi;
+            rb.a2_lo = ci.a2_lo;
+            rb.a2_hi = ci.a2_hi;
+            rb.b2_lo = ci.b2_lo;
+            rb.b2_hi = ci.b2_hi;
+            rb.gy_lo = ci.gy_lo;
+            rb.gy_hi = ci.gy_hi;
+            out[k - 1] = rb;
+        } else {
+            std::memcpy(&out[k - 1], &r, sizeof(Rec));
+        }
         if (msa) continue;
         *done = k;
         // lambda = 0 on a plain direction (the line rule's alpha is always 0):
         // the weights stay and the next search would repeat this one; on a
-        // conjugate direction the next iteration restarts with alpha = 0.  The
-        // empty batch has nothing to iterate.
-        if ((k >= 2u && r.lambda_q16 == 0u && r.alpha_q16 == 0u) || nq == 0u) break;
-        restart = r.lambda_q16 == 0u && r.alpha_q16 > 0u;
+        // conjugate direction the next iteration restarts with alpha = 0 (a
+        // bi-conjugate one: mu = nu = 0).  The empty batch has nothing to iterate.
+        const bool aimed = r.alpha_q16 > 0u || ci.mu_q16 > 0u || ci.nu_q16 > 0u;
+        if ((k >= 2u && r.lambda_q16 == 0u && !aimed) || nq == 0u) break;
+        restart = r.lambda_q16 == 0u && aimed;
     }
 }
 
@@ -538,8 +676,8 @@ int cpd_query_assign(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix
 int cpd_index_flow_step(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f,
                         uint32_t lambda_q16, cpd_flow_info* info) {
     return guarded([&] {
-        cpd_conj_info ci{};
-        checked_step(ix, capacity, f, false, 0u, lambda_q16, &ci);
+        cpd_bi_info ci{};
+        checked_step(ix, capacity, f, Step::plain, 0u, 0u, lambda_q16, &ci);
         if (!info) return;
         *info = cpd_flow_info{};
         info->lambda_q16 = ci.lambda_q16;
@@ -559,8 +697,18 @@ int cpd_index_flow_step(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* 
 int cpd_index_flow_step_conj(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f,
                              uint32_t alpha_q16, uint32_t lambda_q16, cpd_conj_info* info) {
     return guarded([&] {
-        cpd_conj_info ci{};
-        checked_step(ix, capacity, f, true, alpha_q16, lambda_q16, &ci);
+        cpd_bi_info ci{};
+        checked_step(ix, capacity, f, Step::conj, alpha_q16, 0u, lambda_q16, &ci);
+        if (info) *info = conj_info_of(ci);
+    });
+}
+
+int cpd_index_flow_step_bi(cpd_index* ix, const uint32_t* capacity, const cpd_vdf* f,
+                           uint32_t mu_q16, uint32_t nu_q16, uint32_t lambda_q16,
+                           cpd_bi_info* info) {
+    return guarded([&] {
+        cpd_bi_info ci{};
+        checked_step(ix, capacity, f, Step::bi, nu_q16, mu_q16, lambda_q16, &ci);
         if (info) *info = ci;
     });
 }
@@ -583,6 +731,16 @@ int cpd_index_target_fetch(cpd_index* ix, uint64_t* s) {
     });
 }
 
+int cpd_index_target2_fetch(cpd_index* ix, uint64_t* s2) {
+    return guarded([&] {
+        CPD_REQUIRE(ix, CPD_E_ARG, "target2 fetch: null index");
+        CPD_REQUIRE(ix->flow_ready && ix->target_ready && ix->target2_ready, CPD_E_ARG,
+                    "target2 fetch: no second target table resident (cpd_index_flow_step_bi "
+                    "twice first)");
+        fetch_slot_table(ix, ix->tg2_tab.p, ix->fl_out, s2, "target2 fetch");
+    });
+}
+
 int cpd_index_flow_clear(cpd_index* ix) {
     return guarded([&] {
         CPD_REQUIRE(ix, CPD_E_ARG, "flow clear: null index");
@@ -590,8 +748,11 @@ int cpd_index_flow_clear(cpd_index* ix) {
         ix->fl_tab.release();
         ix->fl_out.release();
         ix->tg_tab.release();
+        ix->tg2_tab.release();
         ix->flow_ready = false;
         ix->target_ready = false;
+        ix->target2_ready = false;
+        ix->lambda_prev = 65536u;
     });
 }
 
@@ -608,6 +769,14 @@ int cpd_query_assign_conj(cpd_index* ix, const cpd_search_opts* opts, uint64_t p
                           uint32_t iters, cpd_assign_conj_iter* out, uint32_t* done) {
     return guarded([&] {
         assign_loop(Rule::conj, ix, opts, prefix_bytes, demand, capacity, f, iters, out, done);
+    });
+}
+
+int cpd_query_assign_bi(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                        const uint32_t* demand, const uint32_t* capacity, const cpd_vdf* f,
+                        uint32_t iters, cpd_assign_bi_iter* out, uint32_t* done) {
+    return guarded([&] {
+        assign_loop(Rule::bi, ix, opts, prefix_bytes, demand, capacity, f, iters, out, done);
     });
 }
 

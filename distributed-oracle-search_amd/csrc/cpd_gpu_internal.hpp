@@ -557,6 +557,13 @@ struct cpd_index {
     // a conjugate step, dropped by cpd_index_flow_step and _flow_clear.
     DevBuf<uint64_t> tg_tab;
     bool target_ready = false;
+    // the bi-conjugate step (cpd_index_flow_step_bi, cpd_query_assign_bi): the
+    // second target table S2 (the target before tg_tab's), same layout, and
+    // the lambda of the last such step; every other step and _flow_clear drop
+    // S2, and lambda_prev is 65536 whenever S2 is not resident.
+    DevBuf<uint64_t> tg2_tab;
+    bool target2_ready = false;
+    uint32_t lambda_prev = 65536u;
 };
 
 template <class F>

@@ -862,8 +862,9 @@ int  cpd_index_get_weight_sets(cpd_index* ix, uint32_t* nsets, uint32_t* w /* ns
  * Out of scope: a demand set larger than one prepared batch (write the loop
  * from cpd_query_search_loads(CPD_LOADS_ACCUMULATE) and
  * cpd_index_weights_from_loads(load_div), which is why both are public); a
- * time-dependent search; bi-conjugate Frank-Wolfe (the line search step is
- * cpd_query_assign_line below, the conjugate step cpd_query_assign_conj).   */
+ * time-dependent search.  (The line search step is cpd_query_assign_line
+ * below, the conjugate step cpd_query_assign_conj, the bi-conjugate step
+ * cpd_query_assign_bi.)                                                      */
 typedef struct cpd_assign_iter {
     uint64_t finished;          /* queries with finished == 1 in this iteration  */
     uint64_t sptt_lo, sptt_hi;  /* sum over those of demand[q] * cost[q], under the weights searched with */
@@ -1111,6 +1112,164 @@ int  cpd_query_assign_conj(cpd_index* ix, const cpd_search_opts* opts, uint64_t 
                            const cpd_vdf* f /* load_div ignored */, uint32_t iters /* 1..65535 */,
                            cpd_assign_conj_iter* out /* iters records */,
                            uint32_t* done /* records filled */);
+
+/* The bi-conjugate step — the conjugate step with TWO remembered targets: the
+ * new target is a convex combination of the new all-or-nothing loading and the
+ * last two targets, chosen conjugate to the last two directions (Mitradjieva
+ * and Lindberg's bi-conjugate Frank-Wolfe; the conjugate step still zig-zags
+ * once two directions alternate).  It costs one more table and a wider sums
+ * pass per step, and no extra search.
+ * State.  Beside the flow table X and the target table S1 (the conjugate
+ * step's S, what cpd_index_target_fetch returns) a SECOND TARGET TABLE S2: one
+ * u64 per adjacency slot, Q16, in the flow table's order, carved from the
+ * arena as the others are — the target before S1.  The index also keeps
+ * lambda_prev, the lambda_q16 of the last step made through this call.  S2
+ * exists only after the calls of this section.  cpd_index_flow_clear,
+ * cpd_index_flow_step and cpd_index_flow_step_conj drop S2 (they move X or S1
+ * without knowing it) and nothing else about them changes;
+ * cpd_query_loads_clear and cpd_index_set_weights leave it alone.  Whenever S2
+ * is not resident lambda_prev is 65536.
+ * A procedure, so that two implementations cannot disagree.  Y is the resident
+ * one-plane load table and Yq = Y << 16.  Every counter of Y must be below
+ * 2^30: CPD_E_RANGE otherwise, naming the first offending edge, with nothing
+ * changed, exactly as the conjugate step refuses.  w0, c, the delay function
+ * and the slope h at x = X >> 16 are the conjugate step's, line for line.
+ * The step takes one of three branches, reported in info->branch:
+ * Branch 0 — no flow table resident.  X = S1 = Yq and S2 is not made; the step
+ * reports lambda 65536, evals 0 and every sum, mu, nu, beta and alpha as 0;
+ * lambda_prev = 65536.  mu_q16 and nu_q16 are ignored once in range.
+ * Branch 1 — S2 not resident, or lambda_prev == 65536: either way there is no
+ * usable second direction.  The step is the conjugate step, literally: the
+ * same sums N, M, gy and xw0, the same alpha rule when nu_q16 is CPD_BI_AUTO,
+ * the same target pass, line search and apply.  Every value it writes to X, S1
+ * and the weights and every value it reports equals what
+ * cpd_index_flow_step_conj(CPD_ALPHA_CONJ, lambda_q16) writes and reports from
+ * the same state, bit for bit.  Then S2 takes the S the alpha rule read: the
+ * old S1, or X (before the step) when no target table was resident.  Reported:
+ * alpha_q16, a1 = N, b1 = M, beta0 = 65536 - alpha, beta1 = alpha, beta2 = 0,
+ * mu = nu = 0, a2 = b2 = 0.  An explicit mu_q16 is ignored here.  An explicit
+ * nu_q16 of 0 means alpha = 0, a plain Frank-Wolfe step; any other explicit
+ * nu_q16 is CPD_E_ARG in this branch, naming it.
+ * Branch 2 — otherwise.  Let lp = lambda_prev (below 65536 here).  Per real
+ * slot, every shift arithmetic (a floor):
+ *     d1  = (S1 - X) >> 16
+ *     d2  = (lp * S1 + (65536 - lp) * S2 - 65536 * X) >> 32
+ *     df  = (Yq - X) >> 16
+ *     e21 = (S2 - S1) >> 16
+ * Tables made by steps of this family alone hold values below 2^46: the
+ * bracket in d2 is then below 2^63 in magnitude and every difference below
+ * 2^30.  (After plain flow steps over larger counters the expressions are
+ * taken mod 2^64 and the sums mod 2^128.)  The sums, one pass over the slots:
+ *     A1  = sum of d1 * df  * h          signed 128
+ *     B1  = sum of d1 * d1  * h          unsigned 128
+ *     A2  = sum of d2 * df  * h          signed 128
+ *     B2  = sum of d2 * e21 * h          signed 128
+ *     gy  = sum of (Yq - X) * w(0)       as the conjugate step
+ *     xw0 = sum of X * w(0)
+ * Each term of A1, B1, A2, B2 is below 2^92 in magnitude, fewer than 2^32
+ * slots give less than 2^124.  A slot with d1 == 0 and d2 == 0 skips h.
+ * Then one lane decides; quotients are mathematical integers, saturated at
+ * CPD_BI_MAX = 2^23 - 1 (just under 128.0 in Q16):
+ *     mu  = (A2 == 0 or B2 == 0 or A2, B2 of the same sign) ? 0
+ *           : min(floor(|A2| * 65536 / |B2|), CPD_BI_MAX)
+ *                                             unless mu_q16 is explicit
+ *     nu1 = (B1 == 0 or A1 >= 0) ? 0 : min(floor(|A1| * 65536 / B1), CPD_BI_MAX)
+ *     nu  = min(nu1 + floor(mu * lp / (65536 - lp)), CPD_BI_MAX)
+ *                                             unless nu_q16 is explicit
+ *     beta0 = floor(2^32 / (65536 + mu + nu))
+ *     beta2 = (mu * beta0) >> 16
+ *     beta1 = 65536 - beta0 - beta2
+ * This is mu = -d2'H dFW / d2'H (s2 - s1) and nu = -d1'H dFW / d1'H d1 + mu
+ * lambda / (1 - lambda) of the paper (d1, d2 the two remembered directions, H
+ * the Hessian's diagonal, dFW = y - x), clamped at 0 from below.  beta1 is
+ * never negative: beta0 + beta2 <= beta0 * (65536 + mu) / 65536 <= 2^32 *
+ * (65536 + mu) / ((65536 + mu + nu) * 65536) <= 65536.  The quotients are made
+ * by shift and subtract on 128-bit magnitudes in one lane of the device,
+ * integer part (up to 23 bits) and 16 fraction bits: the remainder stays below
+ * the divisor, below 2^124, so the doubled remainder fits.
+ * New target.  T = floor((beta0 * Yq + beta1 * S1 + beta2 * S2) / 65536), the
+ * sum formed exactly; then S2 <- S1 and S1 <- T, per slot, in place.  mu = nu
+ * = 0 gives T = Yq.  alpha_q16 is reported as 0.
+ * Line search and apply (branches 1 and 2).  Exactly the flow step's with D =
+ * S1 - X (the new S1), as in the conjugate step.
+ * After every branch lambda_prev becomes the lambda taken.
+ * Everything is queued at once and the host reads the outcome once; the range
+ * refusal is decided on the device before the target pass writes.
+ * The exact relative gap before the step is -gy / xw0, from ONE record.
+ * CPD_E_ARG as the conjugate step, and for mu_q16 or nu_q16 in CPD_BI_MAX + 1
+ * .. 0xFFFFFFFE (whatever the branch); cpd_index_target2_fetch without a
+ * resident S2.  On every error X, S1, S2, lambda_prev, the weights and the
+ * load table are untouched.
+ * cpd_index_target2_fetch: S2 in original edge order, as cpd_index_flow_fetch
+ * reads X.                                                                   */
+#define CPD_BI_AUTO 0xFFFFFFFFu
+#define CPD_BI_MAX  8388607u
+typedef struct cpd_bi_info {
+    uint32_t branch;            /* 0, 1 or 2 */
+    uint32_t mu_q16, nu_q16;    /* the mu and nu taken (0 in branches 0 and 1) */
+    uint32_t beta0_q16, beta1_q16, beta2_q16; /* weights of Yq, S1 and S2 in the new target */
+    uint32_t alpha_q16;         /* branch 1: the conjugate step's alpha; else 0 */
+    uint32_t lambda_prev_q16;   /* lambda_prev as the step read it */
+    uint32_t lambda_q16;        /* the step taken */
+    uint32_t evals;             /* evaluations of g made */
+    uint64_t a1_lo, a1_hi;      /* A1, signed 128 (branch 1: N) */
+    uint64_t b1_lo, b1_hi;      /* B1, unsigned 128 (branch 1: M) */
+    uint64_t a2_lo, a2_hi;      /* A2, signed 128 */
+    uint64_t b2_lo, b2_hi;      /* B2, signed 128 */
+    uint64_t gy_lo, gy_hi;      /* gy, signed 128: minus the gap's numerator, Q16 */
+    uint64_t xw0_lo, xw0_hi;    /* sum of X * w(0), unsigned 128, Q16: the gap's denominator */
+    uint64_t g0_lo, g0_hi;      /* g(0) along S1 - X, after S1 is updated, signed 128 */
+    uint64_t tstt_lo, tstt_hi;  /* after the step: sum of (X >> 16) * w', as cpd_vdf_info */
+    uint64_t changed;           /* edges with w' != w0 */
+    double   bi_ms, line_ms, apply_ms; /* device time of the sums, decision and target pass /
+                                          of the evaluations / of the apply pass */
+} cpd_bi_info;
+int  cpd_index_flow_step_bi(cpd_index* ix, const uint32_t* capacity /* m, edge order, >= 1 */,
+                            const cpd_vdf* f /* load_div ignored */,
+                            uint32_t mu_q16 /* 0..CPD_BI_MAX or CPD_BI_AUTO */,
+                            uint32_t nu_q16 /* 0..CPD_BI_MAX or CPD_BI_AUTO */,
+                            uint32_t lambda_q16 /* 0..65536 or CPD_STEP_LINE */,
+                            cpd_bi_info* info /* may be NULL */);
+int  cpd_index_target2_fetch(cpd_index* ix, uint64_t* s2 /* m, edge order, Q16 */);
+
+/* cpd_query_assign_conj with the bi-conjugate step.  The flow table and both
+ * target tables are cleared first (once the first loading has succeeded).
+ * Iteration k makes a fresh loading, forms sptt_k and runs
+ * cpd_index_flow_step_bi with CPD_STEP_LINE and mu = nu = CPD_BI_AUTO, with
+ * one exception: after a record with lambda == 0 and (mu > 0 or nu > 0 or
+ * alpha > 0) the direction went nowhere, and the next iteration passes mu = nu
+ * = 0 — a restart with a plain Frank-Wolfe step.  The loop stops early after
+ * an iteration k >= 2 with lambda == 0 and mu == nu == alpha == 0.  Error
+ * pass-through, the empty batch and *done are as cpd_query_assign_conj; record
+ * k's -gy / xw0 is the exact relative gap before step k.  Afterwards
+ * cpd_index_target_fetch and cpd_index_target2_fetch return the last two
+ * targets.  A record is cpd_assign_line_iter's fields followed by branch, mu,
+ * nu, beta0..2, alpha, a1, b1, a2, b2 and gy.                                */
+typedef struct cpd_assign_bi_iter {
+    uint64_t finished;          /* as cpd_assign_line_iter */
+    uint64_t sptt_lo, sptt_hi;
+    uint64_t tstt_lo, tstt_hi;
+    uint64_t moves, changed;
+    double   search_ms, loads_ms, vdf_ms;
+    uint32_t lambda_q16, evals;
+    uint64_t g0_lo, g0_hi;      /* as cpd_bi_info: along S1 - X */
+    uint64_t xw0_lo, xw0_hi;
+    double   line_ms;           /* the evaluations and the bi-conjugate passes before them */
+    uint32_t branch, mu_q16, nu_q16;   /* as cpd_bi_info */
+    uint32_t beta0_q16, beta1_q16, beta2_q16;
+    uint32_t alpha_q16;
+    uint64_t a1_lo, a1_hi;
+    uint64_t b1_lo, b1_hi;
+    uint64_t a2_lo, a2_hi;
+    uint64_t b2_lo, b2_hi;
+    uint64_t gy_lo, gy_hi;
+} cpd_assign_bi_iter;
+int  cpd_query_assign_bi(cpd_index* ix, const cpd_search_opts* opts, uint64_t prefix_bytes,
+                         const uint32_t* demand /* nq, caller order; NULL = 1 each */,
+                         const uint32_t* capacity /* m, edge order, >= 1 */,
+                         const cpd_vdf* f /* load_div ignored */, uint32_t iters /* 1..65535 */,
+                         cpd_assign_bi_iter* out /* iters records */,
+                         uint32_t* done /* records filled */);
 
 /* ------------------------------------------------------------------------ */
 /* [gpu] Per-kernel device timing (HIP events on the library's stream).      */
